@@ -3,6 +3,8 @@
 DWTForward + DWTInverse, J=3 db4 symmetric, N x 3 x 512 x 512 fp32.
 
     python bench.py --gpus 1 --steps 20 --warmup 5                     # the metric
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full              # + roofline, other configs, CPU baseline
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR  # + the last step's outputs as DIR/<name>.npy
     python bench.py --config dtcwt|scat|cfg5 ...                       # the other BASELINE configs, same flow
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W [--config ...]
@@ -11,6 +13,11 @@ A "step" = one pass of the workload over this rank's batch (dwt / dtcwt: forward
 The batch dimension shards with no data-path collective; the only collective is the one-off broadcast of the filter
 banks from rank 0.  dwt / dtcwt / cfg5 scale weakly (the configured batch per GPU); scat is BASELINE configs[3]:
 256 images split over the ranks (strong).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up (W steps + the clock ramp), times exactly K steps and prints the headline line (`value`,
+`ms_per_step`).  --full adds everything else the line used to carry: the cold figure of a fresh process, the per-part
+durations and the HBM roofline, the per-level tile kernels, device-copy / membench figures, the other configs and the
+CPU baseline.
 """
 import argparse
 import gc
@@ -145,6 +152,48 @@ class Workload(object):
             out = self.run(p)
         return out
 
+    def outputs(self):
+        """(name, tensor) of what a caller of the last step received: the forward's coefficients, then the inverse's
+        reconstruction when the step has one."""
+        outs = _named('forward', self.coefs)
+        if 'i' in self.seq:
+            outs.append(('inverse', self.rec))
+        return outs
+
+
+def _named(prefix, obj):
+    if torch.is_tensor(obj):
+        return [(prefix, obj)]
+    if len(obj) == 2 and isinstance(obj[1], (list, tuple)):     # (yl, yh) of the DWT / DTCWT modules
+        return [(prefix + '_yl', obj[0])] + [(prefix + '_yh%d' % j, h) for j, h in enumerate(obj[1]) if h is not None]
+    return [a for i, o in enumerate(obj) for a in _named('%s_%d' % (prefix, i), o)]
+
+
+DUMP_BUDGET = 60 << 20      # bytes of .npy data one --dump-outputs writes at most
+
+
+def dump_outputs(named, outdir):
+    """--dump-outputs: every array as outdir/<name>.npy, float32 (float64 stays float64).  An array larger than its share of
+    DUMP_BUDGET is written as a fixed sample of its flattened elements: one element drawn (seed 0) from each of `cap` equal
+    slices, so two runs with the same arguments write the same indices and can be compared element for element."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_BUDGET // max(1, len(named))
+    for name, t in named:
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        cap = share // (8 if dt == torch.float64 else 4)
+        n = t.numel()
+        if n > cap:
+            rng = np.random.RandomState(0)
+            lo = np.arange(cap, dtype=np.int64) * n // cap
+            hi = np.arange(1, cap + 1, dtype=np.int64) * n // cap
+            idx = lo + (rng.random_sample(cap) * (hi - lo)).astype(np.int64)
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(outdir, name + '.npy'), t.to(dt).cpu().numpy())
+
 
 class DwtWorkload(Workload):
     key = 'dwt'
@@ -237,8 +286,13 @@ def main():
     ap.add_argument('--config', choices=sorted(WORKLOADS), default='dwt',
                     help='dwt = BASELINE configs[1] (the metric); dtcwt / scat / cfg5 = configs[2] / [3] / [4]')
     ap.add_argument('--batch', type=int, default=0, help='images per GPU (scat: in total); 0 = the BASELINE value')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-other-configs', action='store_true', help='skip the context timings of the other configs')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the cold figure, the per-part roofline, the tile kernels, device copies, the other configs '
+                         'and the CPU baseline (a plain run times the headline steps only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step as DIR/<name>.npy (float32; a fixed sample of a large array)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-other-configs', action='store_true', help='with --full: skip the context timings of the other configs')
     ap.add_argument('--emulate', action='store_true',
                     help='TEST ONLY: run the whole harness on CPU tensors through the host emulation of the kernels '
                          '(tests/emu) with the gloo backend - exercises the multi-rank control flow without a GPU')
@@ -323,8 +377,9 @@ def main():
     gc.collect()
     gc.freeze()
     gc.disable()
-    # 1. cold: a fresh process, W warmup steps, K timed steps - the number a one-shot caller sees
-    dt_cold, _ = timed_region()
+    # 1. cold (--full): a fresh process, W warmup steps, K timed steps - the number a one-shot caller sees
+    if args.full:
+        dt_cold, _ = timed_region()
     # 2. steady: the GPU takes ~20 ms of continuous work to reach its steady clocks (tools/gpu_rampup_probe.py: the first
     #    ~100 launches of a cold process run ~10 % slower); a job of any realistic length lives here.  `value` is this one,
     #    the cold figure is printed beside it.
@@ -332,6 +387,42 @@ def main():
     for _ in range(RAMP_STEPS):
         wl.step()
     dt, out = timed_region()
+    last_outputs = wl.outputs()      # (held: the measurements of --full below run the transforms again)
+
+    def headline():
+        """The result line of a plain run."""
+        pixels = wl.x.numel() * world if wl.scaling == 'weak' else wl.global_batch * wl.C * wl.H * wl.W
+        return {
+            'metric': wl.metric,
+            'value': round(pixels * K / dt / 1e6, 1),
+            'unit': 'Mpixels/s',
+            'n_gpus': world, 'steps': K, 'warmup': args.warmup,
+            'ms_per_step': round(dt / K * 1e3, 4),
+            'host_issue_ms_per_step': round(host_issue[-1], 4),
+            'higher_is_better': True, 'scaling': wl.scaling, 'vs_baseline': None,
+            'clock_ramp_steps_untimed': RAMP_STEPS,
+            'dtype': wl.dtype_name,
+            'data': 'synthetic (HOST EMULATION of the kernels: control-flow test, not a measurement)' if emu else 'synthetic',
+            'config': {'workload': wl.workload, 'global_batch': wl.global_batch,
+                       'parallelism': 'batch-sharded x%d, no data-path collective' % world,
+                       'step': ' + '.join({'f': 'forward', 'i': 'inverse'}[p] for p in wl.seq)},
+        }
+
+    def finish(line):
+        if rank == 0:
+            gc.enable()
+            gc.unfreeze()
+            if args.dump_outputs:
+                dump_outputs(last_outputs, args.dump_outputs)
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+
+    if not args.full:
+        finish(headline() if rank == 0 else None)
+        return
+
     err = None
     if wl.seq == 'fi':
         err = float((out - wl.x).abs().max() / wl.x.abs().max())
@@ -436,7 +527,6 @@ def main():
     if rank == 0:
         per_rank_px = wl.x.numel()
         pixels = per_rank_px * world if wl.scaling == 'weak' else wl.global_batch * wl.C * wl.H * wl.W
-        names = {'f': 'forward', 'i': 'inverse'}
 
         def block(p):
             gbs = wl.bytes[p] / (part_ms[p] * 1e-3) / 1e9
@@ -486,32 +576,19 @@ def main():
             roof['device_copy_kind'] = 'torch.Tensor.copy_ of the input footprint (read + write bytes / time); see membench'
         if mb is not None:
             roof['membench'] = mb
-        out = {
-            'metric': wl.metric,
-            'value': round(pixels * K / dt / 1e6, 1),
-            'unit': 'Mpixels/s',
-            'n_gpus': world, 'steps': K, 'warmup': args.warmup,
-            'ms_per_step': round(dt / K * 1e3, 4),
+        out = headline()
+        out.update({
             'step_ms_events': round(med['S'], 4),
             'timing_consistent': bool(abs(dt / K * 1e3 / med['S'] - 1.0) < 0.05),
-            'host_issue_ms_per_step': round(host_issue[-1], 4),
-            'higher_is_better': True, 'scaling': wl.scaling, 'vs_baseline': None,
-            'clock_ramp_steps_untimed': RAMP_STEPS,
             'cold': {'ms_per_step': round(dt_cold / K * 1e3, 4), 'value': round(pixels * K / dt_cold / 1e6, 1),
                      'what': 'the first %d steps of the process after %d warmup steps, before the %d ramp steps'
                              % (K, args.warmup, RAMP_STEPS)},
-            'dtype': wl.dtype_name, 'data': 'synthetic',
-            'config': {'workload': wl.workload, 'global_batch': wl.global_batch,
-                       'parallelism': 'batch-sharded x%d, no data-path collective' % world,
-                       'step': ' + '.join(names[p] for p in wl.seq)},
             'roofline': roof,
-        }
+        })
         for p in parts:
             out['%s_mpix_s' % ('fwd' if p == 'f' else 'inv')] = round(per_rank_px / (part_ms[p] * 1e-3) / 1e6, 1)
         if err is not None:
             out['roundtrip_rel_err'] = err
-        if emu:
-            out['data'] = 'synthetic (HOST EMULATION of the kernels: control-flow test, not a measurement)'
         if other is not None:
             out['other_configs'] = other
         gc.enable()
@@ -520,10 +597,7 @@ def main():
             out['cpu_baseline'] = cpu_baseline(args)
         else:
             out['cpu_baseline'] = None
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        torch.distributed.barrier()
-        torch.distributed.destroy_process_group()
+    finish(out if rank == 0 else None)
 
 
 _PREFILL = {}

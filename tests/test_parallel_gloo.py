@@ -92,11 +92,11 @@ def _run_bench_emulated(extra):
 def test_bench_other_configs_multi_rank_on_emulator():
     """The same world>1 flow for BASELINE configs[3] (ScatLayer: 256 images - here 5 - split over the ranks, strong
     scaling) and configs[2] (DTCWT forward + inverse, weak), on the host emulation with two gloo ranks."""
-    out = _run_bench_emulated(['--config', 'scat', '--batch', '5'])
+    out = _run_bench_emulated(['--full', '--config', 'scat', '--batch', '5'])
     assert out['n_gpus'] == 2 and out['scaling'] == 'strong' and out['config']['global_batch'] == 5
     assert 'ScatLayer' in out['metric'] and out['config']['step'] == 'forward' and 'inverse' not in out['roofline']
     assert abs(out['value'] - 5 * 3 * 32 * 32 / (out['ms_per_step'] * 1e-3) / 1e6) <= 0.06
-    out = _run_bench_emulated(['--config', 'dtcwt', '--batch', '1'])
+    out = _run_bench_emulated(['--full', '--config', 'dtcwt', '--batch', '1'])
     assert out['scaling'] == 'weak' and out['config']['global_batch'] == 2 and out['roundtrip_rel_err'] < 1e-5
     assert 'inverse' in out['roofline'] and 'closure' in out['roofline']   # (wall-clock noise on the emulator: no value check)
 
@@ -105,9 +105,46 @@ def test_bench_multi_rank_control_flow_on_emulator():
     """bench.py's world>1 branch (process-group init, filter-bank broadcast, barriers, MAX all-reduce of the timed
     region, one JSON line from rank 0 only) executed for real with two gloo ranks on the host emulation of the
     kernels - the driver launches exactly this with nccl on 2/4/8 GPUs."""
-    out = _run_bench_emulated(['--batch', '2'])
+    out = _run_bench_emulated(['--full', '--batch', '2'])
     assert out['n_gpus'] == 2 and out['steps'] == 2 and out['scaling'] == 'weak' and out['cpu_baseline'] is None
     assert out['config']['global_batch'] == 4 and out['roundtrip_rel_err'] < 1e-5
     # whole-job pixels / max-over-ranks time (value is printed with one decimal)
     assert out['value'] > 0 and abs(out['value'] - 2 * 2 * 3 * 64 * 64 / (out['ms_per_step'] * 1e-3) / 1e6) <= 0.06
     assert out['cold']['ms_per_step'] > 0 and ('WlAfbSmall' in out['roofline']['kernel'] or 'WlAfbRows' in out['roofline']['kernel']) and ('WlSfbSmall' in out['roofline']['inverse']['kernel'] or 'WlSfbRows' in out['roofline']['inverse']['kernel'])   # (64 x 64 planes of the emulated run: the small-plane kernels)
+
+
+def test_bench_plain_run_and_dump_outputs_on_emulator(tmp_path):
+    """A plain run (no --full) prints the headline line only; --dump-outputs writes what the last timed step returned:
+    the forward's coefficients and the reconstruction, which equals the seeded input of rank 0."""
+    import numpy as np
+    out = _run_bench_emulated(['--batch', '2', '--dump-outputs', str(tmp_path)])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in out, k
+    assert out['steps'] == 2 and out['ms_per_step'] > 0 and out['dtype'] == 'f32' and out['higher_is_better'] is True
+    assert 'roofline' not in out and 'cold' not in out and 'cpu_baseline' not in out
+    assert abs(out['value'] - 2 * 2 * 3 * 64 * 64 / (out['ms_per_step'] * 1e-3) / 1e6) <= 0.06
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert files == ['forward_yh0.npy', 'forward_yh1.npy', 'forward_yh2.npy', 'forward_yl.npy', 'inverse.npy'], files
+    rec = np.load(str(tmp_path / 'inverse.npy'))
+    x = torch.randn(2, 3, 64, 64, generator=torch.Generator().manual_seed(1234)).numpy()
+    assert rec.dtype == np.float32 and rec.shape == x.shape
+    assert np.abs(rec - x).max() / np.abs(x).max() < 1e-5
+    yh0 = np.load(str(tmp_path / 'forward_yh0.npy'))
+    assert yh0.dtype == np.float32 and yh0.shape == (2, 3, 3, 35, 35)
+
+
+def test_bench_dump_samples_large_outputs(tmp_path, monkeypatch):
+    """An output larger than its share of the dump budget is written as a fixed sample: the same elements on every run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_BUDGET', 2 * 4 * 100)
+    big = torch.arange(10000, dtype=torch.float32).reshape(10, 1000)
+    small = torch.arange(50, dtype=torch.float64)
+    for d in ('a', 'b'):
+        bench.dump_outputs([('big', big), ('small', small)], str(tmp_path / d))
+    a, b = np.load(str(tmp_path / 'a' / 'big.npy')), np.load(str(tmp_path / 'b' / 'big.npy'))
+    assert a.dtype == np.float32 and a.shape == (100,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and np.all(a // 100 == np.arange(100))     # one distinct element from each slice
+    s = np.load(str(tmp_path / 'a' / 'small.npy'))
+    assert s.dtype == np.float64 and np.array_equal(s, small.numpy())

@@ -10,7 +10,7 @@ import sys, json, io, contextlib
 import pytorch_wavelets_amd.ops as o
 o.STRIP_MINW_F16, o.ISTRIP_MINW_F16 = $1, $2
 import bench
-sys.argv = ['bench.py', '--config', 'cfg5', '--steps', '10', '--warmup', '3']
+sys.argv = ['bench.py', '--full', '--config', 'cfg5', '--steps', '10', '--warmup', '3']
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
     bench.main()
