@@ -190,10 +190,14 @@ struct WlRowsSched {
 // NP2 = 1 (round 6): the LL rings have EXACTLY the rows the simulated schedule needs, not the next power of two - a symmetric / reflect pyramid
 // needs L - 1 resident rows per ring for the mirrored rows above the plane plus what the producer runs ahead: 18-24 rows where the power of two is
 // 32, and three levels of a 12- to 16-tap filter on 512 columns are 83-97 KiB with 32-row rings (two workgroups per CU: 80).  The slot of a row is
-// r mod rows by a multiply-high (two scalar instructions more per row than the mask): instantiated for the long filters only.
+// r mod rows by a multiply-high (a few scalar instructions more per row than the mask): instantiated for the long filters only.
+// The mod is a FLOOR mod: periodized levels address their rings by unfolded row numbers, which go down to base = 1 - L/2, and
+// consecutive rows must get distinct slots across 0 (row -1 of a 3-row ring is slot 2, not the slot of row 0).  The bias
+// 64 * rows is a multiple of rows above any -r the plan produces (the launcher checks the slots of the live rows).
 WL_HD int wl_ring_slot(int r, int rows, unsigned magic) {
-    const unsigned q = (unsigned)(((unsigned long long)(unsigned)r * magic) >> 32);     // floor(r / rows) or one less
-    const int sl = r - (int)q * rows;
+    const unsigned u = (unsigned)(r + (rows << 6));                                    // >= 0, same residue
+    const unsigned q = (unsigned)(((unsigned long long)u * magic) >> 32);              // floor(u / rows) or one less
+    const int sl = (int)(u - q * (unsigned)rows);
     return sl >= rows ? sl - rows : sl;
 }
 template <typename T, int LT, int PPR, int D = WL_ROWS_DEPTH, int SAME = 0, int LAT = 0, int ODD = 0, int NP2 = 0>

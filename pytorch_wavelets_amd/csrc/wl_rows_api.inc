@@ -217,6 +217,21 @@ static int wl_afb_rows_launch(WlSrc x, void* yl, void* const* yh, int64_t planes
         if (!bad) break;
     }
     for (int j = 0; j < WL_ROWS_MAXLEV; ++j) a.g[j].ring_magic = (unsigned)(0x100000000ull / (unsigned)a.g[j].ring_rows);
+    if (NP2)
+        for (int j = 1; j < nlev; ++j) {
+            // the rows live at once in a ring (at most ring_rows consecutive row numbers) must sit in distinct slots:
+            // slot(r + rows) == slot(r) over every row number the levels address - the reader's from base up, the producer's
+            // from -hl up (periodization: rows -hl .. -1 are the wrapped bottom rows, wl_dwt_rows.h) - and one period is a permutation
+            const int rows = a.g[j].ring_rows, hi = a.g[j].Hs + 2 * LT + rows;
+            int lo = a.base < 0 ? a.base : 0;
+            if (-a.g[j].hl < lo) lo = -a.g[j].hl;
+            if (-a.g[j - 1].hl < lo) lo = -a.g[j - 1].hl;
+            unsigned long long seen = 0;
+            for (int r = lo; r < lo + rows; ++r) seen |= 1ull << wl_ring_slot(r, rows, a.g[j].ring_magic);
+            if (seen != (rows == 64 ? ~0ull : (1ull << rows) - 1)) return WL_DECLINE(16);
+            for (int r = lo; r + rows <= hi; ++r)
+                if (wl_ring_slot(r + rows, rows, a.g[j].ring_magic) != wl_ring_slot(r, rows, a.g[j].ring_magic)) return WL_DECLINE(16);
+        }
     if (strips == 2 && !can_split) return WL_DECLINE(14);
     {
         int zero_bytes = 0;

@@ -186,6 +186,7 @@ class ScatLayerj1_rot_train_f(Function):
         ctx.mode = mode
         ctx.combine_colour = combine_colour
         ctx.e0 = e0 = 3 if combine_colour else 1              # entry of orientation 0: Z is (N, 3 + 6, h, w) when combining colour
+        ctx.in_hw = tuple(x.shape[-2:])
         save = x.requires_grad
         res = ops.scat_fwd1(x, h0o, h1o, mode, bias, combine_colour, save=save, want_ll=want_ll)
         Z, drdx, drdy = res[:3]
@@ -219,6 +220,11 @@ class ScatLayerj1_rot_train_f(Function):
                 + _scat_bwd1_any(dB, drdx, drdy, h0o, h2o, ctx.mode, ctx.combine_colour)
             if ctx.want_ll:    # the level-1 inverse is linear in (lowpass, highpasses): the lowpass's gradient alone
                 dX = dX + ops.dtcwt_inv1(dll.contiguous(), None, h0o, h1o, ctx.mode)
+            H, W = ctx.in_hw
+            if dX.shape[2] > H:   # gradient of the edge replication for odd sizes (as ScatLayerj1_f.backward)
+                dX = torch.cat((dX[:, :, :H - 1], dX[:, :, H - 1:H] + dX[:, :, H:H + 1]), dim=2)
+            if dX.shape[3] > W:
+                dX = torch.cat((dX[:, :, :, :W - 1], dX[:, :, :, W - 1:W] + dX[:, :, :, W:W + 1]), dim=3)
         return (dX,) + (None,) * 7
 
 
@@ -254,7 +260,8 @@ def scat_layer_j2_rot(x, h0o, h1o, h2o, h0a, h0b, h1a, h1b, h2a, h2b, mode, bias
     if int_to_mode(mode) != 'symmetric':
         raise NotImplementedError()
     n = x.shape[0]
-    if ROT_TRAIN_FUSED and _tf.FUSED_ROT and h1o.numel() == h2o.numel() and h1a.numel() == h2a.numel() and h1b.numel() == h2b.numel():
+    if ROT_TRAIN_FUSED and _tf.FUSED_ROT and x.shape[-2] % 4 == 0 and x.shape[-1] % 4 == 0 and h1o.numel() == h2o.numel() \
+            and h1a.numel() == h2a.numel() and h1b.numel() == h2b.numel():   # (both scales on whole planes: the layer pads odd sizes)
         # Round 6: every band-pass level function differs from the plain one in ONE sub-band - hh is filtered by the third pair on both
         # axes - and the plain fused kernels run with that pair in place of the highpass pair compute it as THEIR hh: each scale is two
         # launches of the plain kernels, the 45 / 135 degree orientations (entries 1 and 4) taken from the second (ScatLayerj1_rot_train_f).

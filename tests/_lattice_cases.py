@@ -505,6 +505,9 @@ def check_tap_state_contract(dev):
 
 # ---- round 6: LL rings sized exactly (WlAfbRows<.., NP2 = 1>): three levels of a long filter on 512 columns in symmetric / reflect mode ---------
 NP2_CASES = [('db8', 'symmetric'), ('db7', 'reflect'), ('db6', 'symmetric'), ('sym8', 'reflect'), ('db10', 'zero')]
+# periodization: the levels address their rings by UNFOLDED row numbers, down to 1 - L/2 (the slot must be a floor mod of them);
+# 18 taps on these planes take the NP2 instantiation by default (wave, mode, (H, W))
+NP2_PER_CASES = [('db9', 'periodization', (256, 512)), ('coif3', 'periodization', (200, 512))]
 
 
 def check_rows_exact_rings(dev, wave, mode, shape=(1, 2, 200, 512), dtype=torch.float32, planes_cut=False, require_np2=True):

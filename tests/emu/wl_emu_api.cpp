@@ -4,3 +4,10 @@
 
 // test hook (emulator only, not part of the C ABI): the size of the emulated chip, for launcher policies that depend on it
 extern "C" void wl_emu_set_cus(int n) { wl_emu_cus_v = n > 0 ? n : 2; }
+// test hook (emulator only): the scheduling choices of wl_backend_emu.h - order 0 alternate (default), 1 forward, 2 reverse,
+// 3 shuffled (seeded); dma 0 late (default), 1 eager
+extern "C" void wl_emu_set_schedule(int order, int dma, unsigned seed) {
+    wl_emu_order_v = order >= 0 && order <= 3 ? order : 0;
+    wl_emu_dma_v = dma == 1 ? 1 : 0;
+    wl_emu_seed_v = seed;
+}

@@ -46,3 +46,29 @@ def chip_of(cus):
         yield
     finally:
         lib.wl_emu_set_cus(2)
+
+
+ORDERS = {'alternate': 0, 'forward': 1, 'reverse': 2, 'shuffled': 3}
+DMA_MODES = {'late': 0, 'eager': 1}
+
+
+@contextlib.contextmanager
+def schedule(order, dma='late', seed=0):
+    """The emulator's scheduling choices (tests/emu/wl_backend_emu.h): the visiting order of the fibres in a barrier phase
+    ('alternate' - the default -, 'forward', 'reverse', 'shuffled' by `seed`) and when an LDS-DMA copy lands ('late' - the
+    default: at the wl_wait_vm that releases it -, 'eager': as soon as its wave has issued it).  Restores the defaults."""
+    handle()
+    lib = ctypes.CDLL(_SO)
+    lib.wl_emu_set_schedule(ORDERS[order], DMA_MODES[dma], ctypes.c_uint(seed & 0xffffffff))
+    try:
+        yield
+    finally:
+        lib.wl_emu_set_schedule(0, 0, ctypes.c_uint(0))
+
+
+def ring_slot_fn():
+    """slot(r, rows): the LL ring slot of row r in a ring of `rows` rows, as the exactly-sized (NP2) rings of WlAfbRows compute it."""
+    handle()
+    f = ctypes.CDLL(_SO).wl_emu_ring_slot
+    f.argtypes, f.restype = [ctypes.c_int, ctypes.c_int], ctypes.c_int
+    return f

@@ -668,6 +668,57 @@ def test_rotationally_symmetric_scatlayer_training_step(shape, dtype, stream):
         NB.check_scat_rot_training('cpu', shape, dtype, expect_stream=stream)
 
 
+@pytest.mark.parametrize('shape', [(1, 2, 23, 37), (2, 1, 24, 37), (1, 1, 25, 40)])
+def test_rotationally_symmetric_training_function_on_odd_sizes(shape):
+    """ScatLayerj1_rot_train_f called directly on an odd-sized input (the kernels extend it by edge replication): its dx has the
+    input's shape, the replicated row / column's gradient folded back, and equals the chain's on the layer's padded input."""
+    from pytorch_wavelets_amd.scatternet import lowlevel as sl_ll
+    rng = np.random.RandomState(31)
+    sl = pw.ScatLayer(biort='near_sym_b_bp')
+    x = torch.tensor(rng.randn(*shape), dtype=torch.float32)
+    H, W = shape[2:]
+    with emu_backend.emulated():
+        xf = x.clone().requires_grad_(True)
+        _, Z = sl_ll.ScatLayerj1_rot_train_f.apply(xf, sl.h0o, sl.h1o, sl.h2o, sl.mode, sl.magbias, False)
+        gz = torch.tensor(rng.randn(*Z.shape), dtype=torch.float32)
+        dx, = torch.autograd.grad(Z, xf, gz)
+        sl_ll.ROT_TRAIN_FUSED = False
+        try:
+            xc = x.clone().requires_grad_(True)
+            xp = torch.cat((xc, xc[:, :, -1:]), dim=2) if H % 2 else xc
+            xp = torch.cat((xp, xp[:, :, :, -1:]), dim=3) if W % 2 else xp
+            Zc = sl_ll.scat_layer_j1_rot(xp, sl.h0o, sl.h1o, sl.h2o, sl.mode, sl.magbias, False)
+            dxc, = torch.autograd.grad(Zc, xc, gz)
+        finally:
+            sl_ll.ROT_TRAIN_FUSED = True
+    assert Z.shape == Zc.shape and float((Z - Zc).abs().max()) <= 1e-5 * float(Zc.abs().max())
+    assert dx.shape == x.shape == dxc.shape, (dx.shape, x.shape)
+    assert float((dx - dxc).abs().max()) <= 2e-5 * float(dxc.abs().max())
+
+
+@pytest.mark.parametrize('shape', [(1, 1, 66, 84), (1, 1, 70, 82)])
+def test_rotationally_symmetric_scatlayerj2_on_sizes_not_a_multiple_of_four(shape):
+    """ScatLayerj2(near_sym_b_bp) on planes whose sides are even but not multiples of 4 (the second scale would see odd planes): the
+    layer's output and dx equal the chain's."""
+    from pytorch_wavelets_amd.scatternet import lowlevel as sl_ll
+    rng = np.random.RandomState(37)
+    layer = pw.ScatLayerj2(biort='near_sym_b_bp', qshift='qshift_b_bp')
+    x = torch.tensor(rng.randn(*shape), dtype=torch.float32)
+    out = {}
+    with emu_backend.emulated():
+        for fused in (True, False):
+            sl_ll.ROT_TRAIN_FUSED = fused
+            try:
+                xg = x.clone().requires_grad_(True)
+                z = layer(xg)
+                dx, = torch.autograd.grad(z, xg, torch.ones_like(z))
+                out[fused] = (z.detach(), dx)
+            finally:
+                sl_ll.ROT_TRAIN_FUSED = True
+    for a, b in zip(out[True], out[False]):
+        assert a.shape == b.shape and float((a - b).abs().max()) <= 3e-5 * float(b.abs().max())
+
+
 @pytest.mark.parametrize('shape,dtype', [((1, 2, 96, 512), torch.float32), ((2, 1, 64, 80), torch.float32)])
 def test_rotationally_symmetric_scatlayerj2_second_order_through_the_layer(shape, dtype):
     import _nearsymb_cases as NB

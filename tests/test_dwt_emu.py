@@ -1148,3 +1148,13 @@ def test_fused_analysis_with_exactly_sized_rings(wave, mode):
     with emu_backend.emulated():
         LC.check_rows_exact_rings('cpu', wave, mode)
         LC.check_rows_exact_rings('cpu', wave, mode, shape=(1, 1, 264, 512), planes_cut=True)
+
+
+@pytest.mark.parametrize('wave,mode,hw', __import__('_lattice_cases').NP2_PER_CASES)
+@pytest.mark.parametrize('order', ['alternate', 'forward'])
+def test_fused_periodization_with_exactly_sized_rings(wave, mode, hw, order):
+    """Row -1 of a periodized level and row 0 must not share a ring slot: with the fibres run forward in every barrier phase
+    the producer's write of one overwrote the other before the consumer read it (relative error 0.4-0.6)."""
+    import _lattice_cases as LC
+    with emu_backend.emulated(), emu_backend.schedule(order):
+        LC.check_rows_exact_rings('cpu', wave, mode, shape=(1, 1) + hw)

@@ -994,3 +994,11 @@ def test_fused_analysis_with_exactly_sized_rings(wave, mode):
     LC.check_rows_exact_rings(DEV, wave, mode, shape=(4, 3, 512, 512))
     LC.check_rows_exact_rings(DEV, wave, mode, shape=(4, 3, 512, 512), planes_cut=True)
     LC.check_rows_exact_rings(DEV, wave, mode, shape=(2, 3, 300, 512), dtype=torch.float16, require_np2=False)   # (float16 rows of 1 KiB: the power-of-two rings fit)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('wave,mode,hw', __import__('_lattice_cases').NP2_PER_CASES)
+def test_fused_analysis_with_exactly_sized_rings_periodization(wave, mode, hw):
+    import _lattice_cases as LC
+    LC.check_rows_exact_rings(DEV, wave, mode, shape=(1, 1) + hw)
+    LC.check_rows_exact_rings(DEV, wave, mode, shape=(4, 3) + hw)
