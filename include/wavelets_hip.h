@@ -9,8 +9,8 @@
  * Conventions
  *   - plain pointers and sizes only; every data/tap pointer is a DEVICE pointer (HBM), tensors
  *     are dense NCHW with N and C collapsed into `planes`; nothing is allocated or freed here.
- *   - `dtype`: WL_F32 0, WL_F16 1 (fp32 accumulate), WL_F64 2.  Taps are float for F32/F16 data
- *     and double for F64 data, in the order the reference's module buffers hold them
+ *   - `dtype`: WL_F32 0, WL_F16 1 (fp32 accumulate), WL_F64 2, WL_BF16 3 (fp32 accumulate).  Taps are
+ *     float for F32 / F16 / BF16 data and double for F64 data, in the order the reference's module buffers hold them
  *     (analysis/DTCWT taps reversed, synthesis taps unreversed).
  *   - `mode`: the reference's integer codes (dwt/lowlevel.py:274-290): 0 zero, 1 symmetric,
  *     2 periodization, 4 reflect, 6 periodic.
@@ -29,6 +29,7 @@ extern "C" {
 #define WL_F32 0
 #define WL_F16 1
 #define WL_F64 2
+#define WL_BF16 3       /* bfloat16 data: the float16 kernels with the other 2-byte format (library version 220) */
 
 #define WL_ERR_MODE (-1)        /* unknown / unsupported padding mode                         */
 #define WL_ERR_SHAPE (-2)       /* inconsistent sizes                                         */
@@ -42,10 +43,11 @@ extern "C" {
  *   100, 200 (rounds 1-4): wl_dwt2d_analysis_fused / _synthesis_fused / _analysis_stream / _synthesis_stream WITHOUT device scratch.
  *   200 (round 5): those four names took a `tap_scratch` pointer in front of `stream` without a version change (a mistake: same
  *          symbol, other arguments).
- *   210 (this header): the four names are back to their round-4 argument lists; the lattice variants that need device scratch are
+ *   210: the four names are back to their round-4 argument lists; the lattice variants that need device scratch are
  *          reached through the new *_ex entry points (tap_scratch + the caller-owned `tap_state`), and
  *          wl_dwt2d_analysis_fused_strided is gone (wl_dwt2d_analysis_fused_ex takes the strides).  A caller built against 2.0.0
- *          must be recompiled against this header (check wl_version() >= 210). */
+ *          must be recompiled against this header (check wl_version() >= 210).
+ *   220 (this header): dtype WL_BF16 (bfloat16 data, float taps) everywhere WL_F16 is accepted; no argument list changes. */
 int wl_version(void);
 const char* wl_backend(void);
 

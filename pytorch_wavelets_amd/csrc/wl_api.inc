@@ -35,7 +35,7 @@ struct WlSfb2dTile {
     static WL_DEV void run(const Args& a, const WlCtx& ctx) { wl_sfb2d_tile_body<T>(a, ctx); }
 };
 
-extern "C" int wl_version(void) { return 210; }
+extern "C" int wl_version(void) { return 220; }
 extern "C" const char* wl_backend(void) { return WL_BACKEND_NAME; }
 extern "C" int wl_dwt_coeff_len(int n, int L, int mode) { return wl_coeff_len(n, L, mode); }
 
@@ -79,6 +79,7 @@ int wl_streaming_off() { return wl_options().no_stream || wl_options().generic_o
     switch (dtype) {                              \
         case WL_F32: { typedef float T; CALL; } break;   \
         case WL_F16: { typedef wl_half T; CALL; } break; \
+        case WL_BF16: { typedef wl_bf16 T; CALL; } break; \
         case WL_F64: { typedef double T; CALL; } break;  \
         default: return WL_ERR_DTYPE;             \
     }
@@ -198,7 +199,11 @@ extern "C" int wl_dwt2d_analysis_strided(const void* x, int64_t x_plane_stride, 
     if (Lw == Lh && dtype != WL_F64 && !wl_options().generic_only) {
         int rc = dtype == WL_F32
                      ? wl_afb_tile_dispatch<float>(st, Lw, x, ll, highs, planes, H, W, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, stream)
-                     : wl_afb_tile_dispatch<wl_half>(st, Lw, x, ll, highs, planes, H, W, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, stream);
+                 : dtype == WL_F16
+                     ? wl_afb_tile_dispatch<wl_half>(st, Lw, x, ll, highs, planes, H, W, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, stream)
+                 : dtype == WL_BF16
+                     ? wl_afb_tile_dispatch<wl_bf16>(st, Lw, x, ll, highs, planes, H, W, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, stream)
+                     : WL_ERR_DTYPE;
         if (rc != WL_ERR_UNSUPPORTED) return rc;
     }
     WL_DISPATCH_DTYPE(dtype, return wl_afb2d_generic<T>(st, x, ll, highs, planes, H, W, h_w_lo, h_w_hi, Lw,
@@ -308,8 +313,13 @@ extern "C" int wl_dwt2d_synthesis(const void* ll, int64_t ll_plane_stride, int l
         int rc = dtype == WL_F32
                      ? wl_sfb_tile_dispatch<float>(Lw, ll, ll_plane_stride, ll_row_stride, highs, y, planes, Kh, Kw,
                                                    OH, OW, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, stream)
-                     : wl_sfb_tile_dispatch<wl_half>(Lw, ll, ll_plane_stride, ll_row_stride, highs, y, planes, Kh,
-                                                     Kw, OH, OW, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, stream);
+                 : dtype == WL_F16
+                     ? wl_sfb_tile_dispatch<wl_half>(Lw, ll, ll_plane_stride, ll_row_stride, highs, y, planes, Kh,
+                                                     Kw, OH, OW, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, stream)
+                 : dtype == WL_BF16
+                     ? wl_sfb_tile_dispatch<wl_bf16>(Lw, ll, ll_plane_stride, ll_row_stride, highs, y, planes, Kh,
+                                                     Kw, OH, OW, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, stream)
+                     : WL_ERR_DTYPE;
         if (rc != WL_ERR_UNSUPPORTED) return rc;
     }
     WL_DISPATCH_DTYPE(dtype, return wl_sfb2d_generic<T>(ll, ll_plane_stride, ll_row_stride, highs, y, planes,
@@ -524,21 +534,27 @@ struct WlDtTile<double> {
 // the streaming level-1 forward over column strips lives in the strip translation unit (wl_strip_api.inc)
 int wl_dtfwd1_strip(const WlDtFwd1Args<float>& f, void* stream);
 int wl_dtfwd1_strip(const WlDtFwd1Args<wl_half>& f, void* stream);
+int wl_dtfwd1_strip(const WlDtFwd1Args<wl_bf16>& f, void* stream);
 int wl_dtfwd1_strip(const WlDtFwd1Args<double>& f, void* stream);
 int wl_dtfwd1_lean(const WlDtFwd1Args<float>& f, void* stream);     // lean level-1 / ScatLayer strip kernels (wl_dtcwt_fused.h)
 int wl_dtfwd1_lean(const WlDtFwd1Args<wl_half>& f, void* stream);
+int wl_dtfwd1_lean(const WlDtFwd1Args<wl_bf16>& f, void* stream);
 int wl_dtfwd1_lean(const WlDtFwd1Args<double>& f, void* stream);
 int wl_dtrot_lean(const WlDtFwd1Args<float>& f, const void* h2, int L2, void* stream);   // ... with the band-pass diagonal (MODE 6)
 int wl_dtrot_lean(const WlDtFwd1Args<wl_half>& f, const void* h2, int L2, void* stream);
+int wl_dtrot_lean(const WlDtFwd1Args<wl_bf16>& f, const void* h2, int L2, void* stream);
 int wl_dtrot_lean(const WlDtFwd1Args<double>& f, const void* h2, int L2, void* stream);
 int wl_dtfwd2_lean(const WlDtFwd2Args<float>& g, void* stream);     // streaming level >= 2 forward (wl_dtcwt_fused.h MODE 4)
 int wl_dtfwd2_lean(const WlDtFwd2Args<wl_half>& g, void* stream);
+int wl_dtfwd2_lean(const WlDtFwd2Args<wl_bf16>& g, void* stream);
 int wl_dtfwd2_lean(const WlDtFwd2Args<double>& g, void* stream);
 int wl_dtinv2_strip(const WlDtInv2Args<float>& f, void* stream);    // streaming level >= 2 inverse (wl_dtcwt_fused.h)
 int wl_dtinv2_strip(const WlDtInv2Args<wl_half>& f, void* stream);
+int wl_dtinv2_strip(const WlDtInv2Args<wl_bf16>& f, void* stream);
 int wl_dtinv2_strip(const WlDtInv2Args<double>& f, void* stream);
 int wl_dtinv1_strip(const WlDtInv1Args<float>& f, void* stream);
 int wl_dtinv1_strip(const WlDtInv1Args<wl_half>& f, void* stream);
+int wl_dtinv1_strip(const WlDtInv1Args<wl_bf16>& f, void* stream);
 int wl_dtinv1_strip(const WlDtInv1Args<double>& f, void* stream);
 
 // small planes, several per workgroup (wl_dtcwt_small.h): even sizes up to 64 x 64, the tabulated level-1 pairs, no colour
@@ -1021,6 +1037,7 @@ extern "C" int wl_dwt2d_analysis_small(const void* x, void* yl, void* const* yh,
     if (planes == 0) return 0;
     if (dtype == WL_F32) return wl_afb_small_run<float>(x, yl, yh, planes, H, W, nlev, h_w_lo, h_w_hi, h_h_lo, h_h_hi, L, mode, stream);
     if (dtype == WL_F16) return wl_afb_small_run<wl_half>(x, yl, yh, planes, H, W, nlev, h_w_lo, h_w_hi, h_h_lo, h_h_hi, L, mode, stream);
+    if (dtype == WL_BF16) return wl_afb_small_run<wl_bf16>(x, yl, yh, planes, H, W, nlev, h_w_lo, h_w_hi, h_h_lo, h_h_hi, L, mode, stream);
     return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
 }
 
@@ -1100,6 +1117,7 @@ extern "C" int wl_dwt2d_synthesis_small(const void* yl, int yl_h, int yl_w, cons
     if (planes == 0) return 0;
     if (dtype == WL_F32) return wl_sfb_small_run<float>(yl, yl_h, yl_w, yh, Kh, Kw, y, planes, nlev, g_w_lo, g_w_hi, g_h_lo, g_h_hi, L, mode, stream);
     if (dtype == WL_F16) return wl_sfb_small_run<wl_half>(yl, yl_h, yl_w, yh, Kh, Kw, y, planes, nlev, g_w_lo, g_w_hi, g_h_lo, g_h_hi, L, mode, stream);
+    if (dtype == WL_BF16) return wl_sfb_small_run<wl_bf16>(yl, yl_h, yl_w, yh, Kh, Kw, y, planes, nlev, g_w_lo, g_w_hi, g_h_lo, g_h_hi, L, mode, stream);
     return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
 }
 

@@ -24,6 +24,7 @@
 #define WL_F32 0
 #define WL_F16 1
 #define WL_F64 2
+#define WL_BF16 3
 
 // boundary-extension codes used INSIDE kernels (the ABI takes the reference's mode ints)
 #define WL_EXT_ZERO 0
@@ -33,6 +34,7 @@
 #define WL_EXT_PER 4       // periodization: odd length repeats the last sample, then wraps
 
 typedef _Float16 wl_half;
+typedef __bf16 wl_bf16;   // bfloat16 data takes the float16 kernels (the 2-byte paths go by sizeof(T)): fp32 taps and accumulators
 
 template <typename T> struct WlAcc { typedef float type; };
 template <> struct WlAcc<double> { typedef double type; };
@@ -105,7 +107,7 @@ template <typename T> inline void wl_store_stream(T* p, T v) { *p = v; }
 // Two adjacent elements (a, b) to sbase + voff: sbase is wave-uniform (a scalar register pair), voff this lane's 32-bit byte
 // offset - the "scalar base + vector offset" form of global_store.  Written as a pointer sum the compiler widens voff to a
 // 64-bit vector address per store (a v_lshl_add_u64 each: 12 per half-batch in the 16-tap strip kernel); float16 pairs are
-// converted two at a time (v_cvt_pk_f16_f32, gfx950) instead of two conversions + v_perm.
+// converted two at a time (v_cvt_pk_f16_f32, gfx950) instead of two conversions + v_perm; bfloat16 pairs likewise (v_cvt_pk_bf16_f32).
 #if defined(__HIPCC__)
 WL_DEV void wl_store2_s(char* sbase, unsigned voff, float a, float b, float*) {
     wl_v2 v = {a, b};
@@ -115,6 +117,12 @@ WL_DEV void wl_store2_s(char* sbase, unsigned voff, float a, float b, _Float16*)
     typedef _Float16 H2 __attribute__((ext_vector_type(2)));
     const wl_v2 f = {a, b};
     const unsigned p = __builtin_bit_cast(unsigned, __builtin_convertvector(f, H2));     // v_cvt_pk_f16_f32 (gfx950)
+    asm volatile("global_store_dword %0, %1, %2" :: "v"(voff), "v"(p), "s"(sbase) : "memory");
+}
+WL_DEV void wl_store2_s(char* sbase, unsigned voff, float a, float b, __bf16*) {
+    typedef __bf16 B2 __attribute__((ext_vector_type(2)));
+    const wl_v2 f = {a, b};
+    const unsigned p = __builtin_bit_cast(unsigned, __builtin_convertvector(f, B2));     // v_cvt_pk_bf16_f32 (gfx950), nearest even
     asm volatile("global_store_dword %0, %1, %2" :: "v"(voff), "v"(p), "s"(sbase) : "memory");
 }
 WL_DEV void wl_store2_s(char* sbase, unsigned voff, float a, float b, double*) {

@@ -100,6 +100,7 @@ extern "C" int wl_dwt1d_analysis_fused(const void* x, void* lo, void* const* hig
     return wl_dwt1d_fused_any<T_>(a, L, stream);
     if (dtype == WL_F32) { WL_FILL(float) }
     if (dtype == WL_F16) { WL_FILL(wl_half) }
+    if (dtype == WL_BF16) { WL_FILL(wl_bf16) }
 #undef WL_FILL
     return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
 }
@@ -170,6 +171,7 @@ extern "C" int wl_dwt1d_synthesis_fused(const void* lo, int n_lo, const void* co
     return wl_idwt1d_fused_any<T_>(a, L, stream);
     if (dtype == WL_F32) { WL_FILL(float) }
     if (dtype == WL_F16) { WL_FILL(wl_half) }
+    if (dtype == WL_BF16) { WL_FILL(wl_bf16) }
 #undef WL_FILL
     return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
 }

@@ -425,6 +425,9 @@ extern "C" int wl_dwt2d_analysis_fused_ex(const void* xp, int64_t x_plane_stride
     if (dtype == WL_F16)
         return planes == 0 ? 0 : wl_afb_rows_dispatch<wl_half>(L, x, yl, yh, planes, H, W, nlev, h_w_lo,
                                                               h_w_hi, h_h_lo, h_h_hi, mode, strips, stream, hints, (float*)tap_scratch, tap_state);
+    if (dtype == WL_BF16)
+        return planes == 0 ? 0 : wl_afb_rows_dispatch<wl_bf16>(L, x, yl, yh, planes, H, W, nlev, h_w_lo,
+                                                              h_w_hi, h_h_lo, h_h_hi, mode, strips, stream, hints, (float*)tap_scratch, tap_state);
     return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
 }
 
@@ -769,6 +772,9 @@ extern "C" int wl_dwt2d_synthesis_fused_ex(const void* yl, int64_t yl_plane_stri
                                            nlev, g_w_lo, g_w_hi, g_h_lo, g_h_hi, strips, stream, hints, (float*)tap_scratch, tap_state, per);
     if (dtype == WL_F16)
         return wl_sfb_rows_dispatch<wl_half>(L, yl, yl_plane_stride, yl_row_stride, yl_h, yl_w, yh, Kh, Kw, y, planes,
+                                             nlev, g_w_lo, g_w_hi, g_h_lo, g_h_hi, strips, stream, hints, (float*)tap_scratch, tap_state, per);
+    if (dtype == WL_BF16)
+        return wl_sfb_rows_dispatch<wl_bf16>(L, yl, yl_plane_stride, yl_row_stride, yl_h, yl_w, yh, Kh, Kw, y, planes,
                                              nlev, g_w_lo, g_w_hi, g_h_lo, g_h_hi, strips, stream, hints, (float*)tap_scratch, tap_state, per);
     return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
 }

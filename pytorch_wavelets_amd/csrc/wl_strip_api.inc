@@ -254,6 +254,9 @@ extern "C" int wl_dwt2d_analysis_stream_ex(const void* x, int64_t x_plane_stride
     if (dtype == WL_F16)
         return wl_afb_strip_dispatch<wl_half>(L, x, x_plane_stride, x_row_stride, ll, ll_plane_stride, ll_row_stride, highs,
                                               planes, H, W, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, policy, stream, (float*)tap_scratch, tap_state);
+    if (dtype == WL_BF16)
+        return wl_afb_strip_dispatch<wl_bf16>(L, x, x_plane_stride, x_row_stride, ll, ll_plane_stride, ll_row_stride, highs,
+                                              planes, H, W, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, policy, stream, (float*)tap_scratch, tap_state);
     return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
 }
 
@@ -440,6 +443,9 @@ extern "C" int wl_dwt2d_synthesis_stream_ex(const void* ll, int64_t ll_plane_str
     if (dtype == WL_F16)
         return wl_sfb_strip_dispatch<wl_half>(L, ll, ll_plane_stride, ll_row_stride, highs, y, planes, Kh, Kw, OH, OW,
                                               g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, policy, stream, (float*)tap_scratch, tap_state);
+    if (dtype == WL_BF16)
+        return wl_sfb_strip_dispatch<wl_bf16>(L, ll, ll_plane_stride, ll_row_stride, highs, y, planes, Kh, Kw, OH, OW,
+                                              g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, policy, stream, (float*)tap_scratch, tap_state);
     return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
 }
 
@@ -528,6 +534,7 @@ static int wl_dtfwd1_strip_any(const WlDtFwd1Args<T>& f, void* stream) {
 }
 int wl_dtfwd1_strip(const WlDtFwd1Args<float>& f, void* stream) { return wl_dtfwd1_strip_any<float>(f, stream); }
 int wl_dtfwd1_strip(const WlDtFwd1Args<wl_half>& f, void* stream) { return wl_dtfwd1_strip_any<wl_half>(f, stream); }
+int wl_dtfwd1_strip(const WlDtFwd1Args<wl_bf16>& f, void* stream) { return wl_dtfwd1_strip_any<wl_bf16>(f, stream); }
 int wl_dtfwd1_strip(const WlDtFwd1Args<double>&, void*) { return WL_ERR_UNSUPPORTED; }
 
 // ---- streaming level-1 DTCWT inverse over column strips ---------------------------------------------------------------
@@ -603,6 +610,7 @@ static int wl_dtinv1_strip_any(const WlDtInv1Args<T>& f, void* stream) {
 }
 int wl_dtinv1_strip(const WlDtInv1Args<float>& f, void* stream) { return wl_dtinv1_strip_any<float>(f, stream); }
 int wl_dtinv1_strip(const WlDtInv1Args<wl_half>& f, void* stream) { return wl_dtinv1_strip_any<wl_half>(f, stream); }
+int wl_dtinv1_strip(const WlDtInv1Args<wl_bf16>& f, void* stream) { return wl_dtinv1_strip_any<wl_bf16>(f, stream); }
 int wl_dtinv1_strip(const WlDtInv1Args<double>&, void*) { return WL_ERR_UNSUPPORTED; }
 
 // ---- levels 1 + 2 of the DTCWT forward in one streaming launch (wl_dtcwt_fused.h) ----------------------------------------
@@ -692,6 +700,8 @@ extern "C" int wl_dtcwt_fwd_level12(const void* x, void* highs1, void* ll2, void
         return wl_dtfwd12_any<float>(x, highs1, ll2, highs2, planes, H, W, h0o, L0, h1o, L1, h0a, h0b, h1a, h1b, LQ, policy, stream);
     if (dtype == WL_F16)
         return wl_dtfwd12_any<wl_half>(x, highs1, ll2, highs2, planes, H, W, h0o, L0, h1o, L1, h0a, h0b, h1a, h1b, LQ, policy, stream);
+    if (dtype == WL_BF16)
+        return wl_dtfwd12_any<wl_bf16>(x, highs1, ll2, highs2, planes, H, W, h0o, L0, h1o, L1, h0a, h0b, h1a, h1b, LQ, policy, stream);
     return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
 }
 
@@ -777,9 +787,11 @@ static int wl_dtrot_lean_any(const WlDtFwd1Args<T>& f, const void* h2, int L2, v
 }
 int wl_dtrot_lean(const WlDtFwd1Args<float>& f, const void* h2, int L2, void* stream) { return wl_dtrot_lean_any<float>(f, h2, L2, stream); }
 int wl_dtrot_lean(const WlDtFwd1Args<wl_half>& f, const void* h2, int L2, void* stream) { return wl_dtrot_lean_any<wl_half>(f, h2, L2, stream); }
+int wl_dtrot_lean(const WlDtFwd1Args<wl_bf16>& f, const void* h2, int L2, void* stream) { return wl_dtrot_lean_any<wl_bf16>(f, h2, L2, stream); }
 int wl_dtrot_lean(const WlDtFwd1Args<double>&, const void*, int, void*) { return WL_ERR_UNSUPPORTED; }
 int wl_dtfwd1_lean(const WlDtFwd1Args<float>& f, void* stream) { return wl_dtlean1_any<float>(f, stream); }
 int wl_dtfwd1_lean(const WlDtFwd1Args<wl_half>& f, void* stream) { return wl_dtlean1_any<wl_half>(f, stream); }
+int wl_dtfwd1_lean(const WlDtFwd1Args<wl_bf16>& f, void* stream) { return wl_dtlean1_any<wl_bf16>(f, stream); }
 int wl_dtfwd1_lean(const WlDtFwd1Args<double>&, void*) { return WL_ERR_UNSUPPORTED; }
 
 // ---- streaming level >= 2 DTCWT inverse over column strips (wl_dtcwt_fused.h) ----------------------------------------------
@@ -826,6 +838,7 @@ static int wl_dtinv2_strip_any(const WlDtInv2Args<T>& f, void* stream) {
 }
 int wl_dtinv2_strip(const WlDtInv2Args<float>& f, void* stream) { return wl_dtinv2_strip_any<float>(f, stream); }
 int wl_dtinv2_strip(const WlDtInv2Args<wl_half>& f, void* stream) { return wl_dtinv2_strip_any<wl_half>(f, stream); }
+int wl_dtinv2_strip(const WlDtInv2Args<wl_bf16>& f, void* stream) { return wl_dtinv2_strip_any<wl_bf16>(f, stream); }
 int wl_dtinv2_strip(const WlDtInv2Args<double>&, void*) { return WL_ERR_UNSUPPORTED; }
 
 // ---- level >= 2 forward alone on the stagers and level-2 lanes of the fused kernel (MODE 4) ------------------------------------
@@ -889,5 +902,6 @@ static int wl_dtfwd2_lean_any(const WlDtFwd2Args<T>& g, void* stream) {
 }
 int wl_dtfwd2_lean(const WlDtFwd2Args<float>& g, void* stream) { return wl_dtfwd2_lean_any<float>(g, stream); }
 int wl_dtfwd2_lean(const WlDtFwd2Args<wl_half>& g, void* stream) { return wl_dtfwd2_lean_any<wl_half>(g, stream); }
+int wl_dtfwd2_lean(const WlDtFwd2Args<wl_bf16>& g, void* stream) { return wl_dtfwd2_lean_any<wl_bf16>(g, stream); }
 int wl_dtfwd2_lean(const WlDtFwd2Args<double>&, void*) { return WL_ERR_UNSUPPORTED; }
 #endif   // WL_STRIP_PARTS & 4

@@ -11,7 +11,7 @@ from .. import ops
 
 def prep_filt(h, c, transpose=False):
     """Column-vector filter, REVERSED, shape (c,1,L,1) (or (c,1,1,L) with transpose), default dtype."""
-    h = np.asarray(h.detach().cpu().numpy() if isinstance(h, torch.Tensor) else h, dtype=np.float64)
+    h = np.asarray(h.detach().cpu().double().numpy() if isinstance(h, torch.Tensor) else h, dtype=np.float64)   # (numpy has no bfloat16)
     h = h.reshape(-1)[::-1].reshape(1, 1, -1, 1)
     h = np.repeat(h, repeats=c, axis=0)
     if transpose:

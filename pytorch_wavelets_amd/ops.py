@@ -7,7 +7,7 @@ import torch
 
 from . import _lib
 
-_DTYPES = {torch.float32: 0, torch.float16: 1, torch.float64: 2}
+_DTYPES = {torch.float32: 0, torch.float16: 1, torch.float64: 2, torch.bfloat16: 3}   # bfloat16 takes the float16 kernels
 _TEST_BACKEND = None   # set ONLY by tests/emu_backend.py (host emulation of the kernel sources)
 
 
@@ -17,7 +17,7 @@ def _backend():
 
 def _check_tensor(t, name):
     if t.dtype not in _DTYPES:
-        raise TypeError('%s: unsupported dtype %s (float16/float32/float64)' % (name, t.dtype))
+        raise TypeError('%s: unsupported dtype %s (float16/bfloat16/float32/float64)' % (name, t.dtype))
     if not t.is_cuda and _TEST_BACKEND is None:
         raise RuntimeError('%s is on %s: pytorch_wavelets_amd runs on MI355X only (HIP kernels, '
                            'no CPU fallback). Move the module and its input to a cuda device.'
@@ -364,10 +364,10 @@ def afb2d_fused(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, nlev, strips=None, whol
     # (periodization with 12 taps: its odd-cell instantiations are the lattice variant and the two-bank direct form, which spills)
     lattice = (same and qmf and ROWS_LATTICE and L in (8, 10, 12, 14, 16, 18, 20) and L >= ROWS_LATTICE_MIN
                and (L > 12 or x.numel() >= LATTICE_MIN_ELEMS or (mode == 2 and L == 12)))
-    # (float16-ROUNDED 20-tap banks - the buffers of a `.half()` module - are no orthogonal pair to within the lattice's tolerance (residue 9e-4,
+    # (float16- or bfloat16-ROUNDED 20-tap banks - the buffers of a `.half()` / bfloat16 module - are no orthogonal pair to within the lattice's tolerance (residue 9e-4,
     # csrc/wl_lattice.h): the examination rejects them and the armed two-bank 20-tap kernel, which spills, would do the work - 0.70 ms against
     # 0.32 on the strip kernels for 512x1x512^2 J = 2, tools/gpu_r6_per.py deep)
-    if L == 20 and h_w_lo.dtype == torch.float16 and strips == 0:      # (the engine's policy; a forced launch is taken)
+    if L == 20 and h_w_lo.element_size() == 2 and strips == 0:      # (the engine's policy; a forced launch is taken)
         return None
     if (x.dtype == torch.float64 or nlev < 1 or nlev > 3 or h_h_lo.numel() != L or L % 2 or (L > 12 and not lattice)
             or (nlev > 1 and mode not in (0, 1, 2, 4)) or x.numel() == 0 or (mode == 2 and not ROWS_PER and (nlev > 1 or L % 4 == 0))
@@ -1025,7 +1025,7 @@ def dtcwt_fwd12(x, h0o, h1o, h0a, h0b, h1a, h1b, mode, force=False):
     plane meet the column lowpass taps in reverse order, so no symmetry of h0o is assumed)."""
     _check_tensor(x, 'x')
     N, C, H, W = x.shape
-    if mode != 1 or H % 4 or W % 4 or x.dtype not in (torch.float32, torch.float16):
+    if mode != 1 or H % 4 or W % 4 or x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
         return None
     force = force or STREAM_FORCE
     key = ('dt12', x.device, x.dtype, N * C, H, W, h0o.numel(), h1o.numel(), h0a.numel(), mode)
@@ -1125,7 +1125,7 @@ def dtcwt_inv21(ll2, highs2, highs1, g0o, g1o, g0a, g0b, g1a, g1b, mode, force=F
     if highs2 is None or highs1 is None or highs1.dim() != 6 or highs2.dim() != 6:
         return None
     N, C, h, w = ll2.shape
-    if (mode != 1 or h % 2 or w % 2 or ll2.dtype not in (torch.float32, torch.float16) or highs1.dtype != ll2.dtype
+    if (mode != 1 or h % 2 or w % 2 or ll2.dtype not in (torch.float32, torch.float16, torch.bfloat16) or highs1.dtype != ll2.dtype
             or highs2.dtype != ll2.dtype or tuple(highs2.shape) != (N, C, 6, h // 2, w // 2, 2)
             or tuple(highs1.shape) != (N, C, 6, h, w, 2) or ll2.numel() == 0):
         return None
