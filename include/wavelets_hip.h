@@ -404,6 +404,31 @@ int wl_swt2d_level(const void* x, int64_t x_ps, void* y, int dtype, int64_t plan
                    const void* h_w_lo, const void* h_w_hi, const void* h_h_lo, const void* h_h_hi, int Lw, int Lh,
                    int dilation, int ext, void* stream);
 
+/* The TRANSPOSE of wl_swt2d_level in ONE launch (csrc/wl_iswt2d.h): y (planes,4,H,W) through the plane stride y_ps (the four
+ * sub-bands 2 r + b of a plane dense) -> x (planes,H,W) dense,
+ *   x = scale * sum_{r,b} A_r(h_w)^T A_b(h_h)^T y[2 r + b]          A = the matrix of the analysis along one axis.
+ * scale 1: the backward of afb2d_atrous - what autograd derives upstream from mypad + conv2d (dwt/lowlevel.py:475-521) and
+ * this engine has to state itself.  scale 1/4, ext 3 (periodic) and the synthesis taps as the bank: one level of the inverse
+ * stationary transform, the intent of dwt/swt_inverse.py (dead code upstream: no imports, it calls the decimated sfb2d, its
+ * sfb1d_atrous divides by 2*dilation); 1/4 sum_{r,b} B_rb^T A_rb = I for every pywt wavelet and dilation.
+ * ll (planes,H,W) through ll_ps, rows dense: ll_mode 0 none (ll NULL), 1 replace - sub-band 0 is read from ll (y may then be
+ * NULL: the other three are zeros), 2 add - ll is added to sub-band 0 (the gradient that arrives from the next level).
+ * Taps as for wl_swt2d_level.  ext 0 zero and 3 periodic; returns WL_ERR_UNSUPPORTED for 1 symmetric, 2 reflect, 5 replicate
+ * (several extended samples fold onto one), for odd L * dilation and for dilated filters too long for a tile in LDS: callers
+ * then chain wl_corr1d_adj. */
+int wl_iswt2d_level(const void* y, int64_t y_ps, const void* ll, int64_t ll_ps, int ll_mode, void* x, int dtype, int64_t planes,
+                    int H, int W, const void* h_w_lo, const void* h_w_hi, const void* h_h_lo, const void* h_h_hi, int Lw, int Lh,
+                    int dilation, int ext, double scale, void* stream);
+
+/* The transpose of the unit-step wl_corr1d along the middle axis: with y_b[k] = sum_t h_b[t] * ext(x, start + k + tap_step*t),
+ * k in [0,K),  dx = scale * (A_0^T y0 + A_1^T y1):  y0 / y1 (outer,K,inner) through their outer strides (elements; y1 / h1
+ * nullable) -> dx (outer,n,inner) dense.  Every rule of wl_corr1d but the periodizations (ext 0, 1, 2, 3, 5), any dilation,
+ * any K, pads of any length (the samples that fold onto one are walked).  Replaces the autograd of afb1d_atrous
+ * (dwt/lowlevel.py:175-223) and, with the synthesis taps and scale 1/2, states sfb1d_atrous of dwt/swt_inverse.py. */
+int wl_corr1d_adj(const void* y0, int64_t y0_outer_stride, const void* y1, int64_t y1_outer_stride, void* dx, int dtype,
+                  int64_t outer, int n, int64_t inner, int K, const void* h0, const void* h1, int ntaps, int start, int tap_step,
+                  int ext, double scale, void* stream);
+
 /* 1-D two-channel synthesis bank along the middle axis = sfb1d (dwt/lowlevel.py:226-271; SFB1D.forward :697-727 and
  * AFB1D.backward :409-424): lo, hi (outer, K, inner) [hi may be NULL = zeros] -> y (outer, ny, inner) with
  * ny <= 2K-L+2 (2K for periodization, whose single fold of the wrapped tail is reproduced literally). */

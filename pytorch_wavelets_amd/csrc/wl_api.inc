@@ -14,6 +14,7 @@
 #include "wl_dwt_small.h"
 #include "wl_filt1d.h"
 #include "wl_swt2d.h"
+#include "wl_iswt2d.h"
 #include "wl_dtcwt_kernels.h"
 #include "wl_dtcwt_tile.h"
 #include "wl_dtcwt_rot.h"
@@ -1175,6 +1176,92 @@ extern "C" int wl_swt2d_level(const void* x, int64_t x_ps, void* y, int dtype, i
     if ((int64_t)H * W >= (1LL << 30)) return WL_ERR_UNSUPPORTED;
     if (planes == 0) return 0;
     WL_DISPATCH_DTYPE(dtype, return wl_swt2d_run<T>(x, x_ps, y, planes, H, W, h_w_lo, h_w_hi, h_h_lo, h_h_hi, Lw, Lh, dilation, ext, stream));
+    return 0;
+}
+
+// ---- the transpose of that level: backward of the stationary transform and one level of its inverse (wl_iswt2d.h) ----
+template <typename T, int LT>
+static int wl_iswt2d_launch(WlSwtInvArgs<T>& a, void* stream) {
+    return wl_launch<WlSwtInvLevel<T, LT> >(a, a.nblocks, (size_t)a.lds_bytes, stream);
+}
+
+template <typename T>
+static int wl_iswt2d_run(const void* y, int64_t y_ps, const void* ll, int64_t ll_ps, int ll_mode, void* x, int64_t planes, int H, int W,
+                         const void* h_w_lo, const void* h_w_hi, const void* h_h_lo, const void* h_h_hi, int Lw, int Lh, int dilation,
+                         int ext, double scale, void* stream) {
+    typedef typename WlAcc<T>::type A;
+    WlSwtInvArgs<T> a;
+    a.y = (const T*)y; a.ll = (const T*)ll; a.x = (T*)x; a.y_ps = y_ps; a.ll_ps = ll_ps; a.ll_mode = ll_mode; a.planes = planes;
+    a.hw0 = (const A*)h_w_lo; a.hw1 = (const A*)h_w_hi; a.hh0 = (const A*)h_h_lo; a.hh1 = (const A*)h_h_hi;
+    a.scale = (A)scale;
+    a.H = H; a.W = W; a.Lw = Lw; a.Lh = Lh; a.d = dilation; a.ext = ext;
+    a.sw = -((Lw * dilation) / 2); a.sh = -((Lh * dilation) / 2);
+    const int hw = (Lw - 1) * dilation;
+    const int hh = (Lh - 1) * dilation;
+    // the tallest tile whose staged pair of bands and row-filtered pairs fit 64 KiB of LDS (two workgroups per CU); what fits
+    // no tile of four rows so (the staged pair is twice the forward's input tile) may take a CU's whole 160 KiB: one
+    // workgroup per CU is still one pass over the data, where the single-axis kernel needs three
+    if (hw > 4096 || hh > 4096) return WL_ERR_UNSUPPORTED;         // (and the byte counts below stay far from 2^31)
+    a.in_pitch = 64 + hw + 1;
+    int TH = 32, budget = 64 * 1024;
+    for (;; TH /= 2) {
+        if (TH < 4) {
+            if (budget > 64 * 1024) return WL_ERR_UNSUPPORTED;     // long dilated filters: the single-axis kernel
+            TH = 32; budget = 160 * 1024;
+        }
+        a.mid_off = wl_align_up((TH + hh) * a.in_pitch * 2 * (int)sizeof(A), 16);
+        a.lds_bytes = a.mid_off + (TH + hh) * 64 * 2 * (int)sizeof(A);
+        if (a.lds_bytes <= budget) break;
+    }
+    a.TH = TH;
+    a.tiles_x = wl_cdiv(W, 64); a.tiles_y = wl_cdiv(H, TH);
+    a.nblocks = planes * a.tiles_x * a.tiles_y;
+    if (Lw == Lh) switch (Lw) {
+        case 2: return wl_iswt2d_launch<T, 2>(a, stream);
+        case 4: return wl_iswt2d_launch<T, 4>(a, stream);
+        case 6: return wl_iswt2d_launch<T, 6>(a, stream);
+        case 8: return wl_iswt2d_launch<T, 8>(a, stream);
+        case 10: return wl_iswt2d_launch<T, 10>(a, stream);
+        case 12: return wl_iswt2d_launch<T, 12>(a, stream);
+        case 16: return wl_iswt2d_launch<T, 16>(a, stream);
+        case 20: return wl_iswt2d_launch<T, 20>(a, stream);
+        default: break;
+    }
+    return wl_iswt2d_launch<T, 0>(a, stream);
+}
+
+extern "C" int wl_iswt2d_level(const void* y, int64_t y_ps, const void* ll, int64_t ll_ps, int ll_mode, void* x, int dtype,
+                               int64_t planes, int H, int W, const void* h_w_lo, const void* h_w_hi, const void* h_h_lo,
+                               const void* h_h_hi, int Lw, int Lh, int dilation, int ext, double scale, void* stream) {
+    if (planes < 0 || H < 1 || W < 1 || dilation < 1) return WL_ERR_SHAPE;
+    if (Lw < 1 || Lh < 1 || Lw > WL_MAX_TAPS || Lh > WL_MAX_TAPS) return WL_ERR_TAPS;
+    if (ext < 0 || ext > WL_EXT_REPLICATE || ext == WL_EXT_PER) return WL_ERR_MODE;
+    if (ll_mode < 0 || ll_mode > 2 || (ll_mode != 0) != (ll != nullptr) || (!y && ll_mode != 1)) return WL_ERR_SHAPE;
+    // the mirror and replicate rules fold several extended samples onto one: the single-axis kernel walks them
+    if (ext != WL_EXT_ZERO && ext != WL_EXT_PERIODIC) return WL_ERR_UNSUPPORTED;
+    if ((Lw * dilation) % 2 || (Lh * dilation) % 2) return WL_ERR_UNSUPPORTED;   // (the level changes size: not square)
+    if ((int64_t)H * W >= (1LL << 30)) return WL_ERR_UNSUPPORTED;
+    if (planes == 0) return 0;
+    WL_DISPATCH_DTYPE(dtype, return wl_iswt2d_run<T>(y, y_ps, ll, ll_ps, ll_mode, x, planes, H, W, h_w_lo, h_w_hi, h_h_lo, h_h_hi, Lw, Lh,
+                                                     dilation, ext, scale, stream));
+    return 0;
+}
+
+extern "C" int wl_corr1d_adj(const void* y0, int64_t y0_outer_stride, const void* y1, int64_t y1_outer_stride, void* dx, int dtype,
+                             int64_t outer, int n, int64_t inner, int K, const void* h0, const void* h1, int ntaps, int start,
+                             int tap_step, int ext, double scale, void* stream) {
+    if (outer < 0 || n < 1 || inner < 1 || K < 0 || ntaps < 1 || ntaps > WL_MAX_TAPS || tap_step < 1 || !y0) return WL_ERR_SHAPE;
+    if (y1 && !h1) return WL_ERR_SHAPE;
+    if (ext < 0 || ext > WL_EXT_REPLICATE || ext == WL_EXT_PER) return WL_ERR_MODE;
+    if (outer == 0) return 0;
+    WL_DISPATCH_DTYPE(dtype, {
+        typedef typename WlAcc<T>::type A;
+        WlCorr1dAdjArgs<T> a;
+        a.y0 = (const T*)y0; a.y1 = (const T*)y1; a.dx = (T*)dx; a.h0 = (const A*)h0; a.h1 = (const A*)h1; a.scale = (A)scale;
+        a.outer = outer; a.inner = inner; a.y0_os = y0_outer_stride; a.y1_os = y1_outer_stride;
+        a.n = n; a.K = K; a.nt = ntaps; a.start = start; a.dstep = tap_step; a.ext = ext;
+        return wl_launch<WlCorr1dAdj<T> >(a, wl_cdiv64(outer * n * inner, 256), 0, stream);
+    });
     return 0;
 }
 

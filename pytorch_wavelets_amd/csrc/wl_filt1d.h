@@ -101,6 +101,81 @@ struct WlCorr1d {
     }
 };
 
+// The transpose of the unit-step correlation above (two tap sets): with y_b[k] = sum_t h_b[t] * ext(x, start + k + dstep*t),
+// k in [0,K),
+//     dx[m] = scale * sum_{e : ext(e) == m, start <= e <= start + K-1 + dstep*(nt-1)} z[e]
+//     z[e]  = sum_b sum_t h_b[t] * y_b[e - start - dstep*t]                       (y_b zero outside [0,K))
+// One thread per dx sample.  The extended positions e that the rule maps onto m are arithmetic progressions, walked with as
+// many folds as the pad is long: zero {m}; periodic m + n q; symmetric m + 2n q and -1-m + 2n q; reflect +-m + (2n-2) q (the two
+// coincide at m = 0 and m = n-1: counted once); replicate every e <= 0 for m = 0 and every e >= n-1 for m = n-1.
+// This is what autograd derives upstream for afb1d_atrous (dwt/lowlevel.py:175-223: mypad + conv2d), for any axis, dilation
+// and K; the fused level kernel (wl_iswt2d.h) hands over what it declines.
+template <typename T>
+struct WlCorr1dAdjArgs {
+    typedef typename WlAcc<T>::type A;
+    const T* y0; const T* y1;          // (outer, K, inner) through their outer strides; y1 may be nullptr
+    T* dx;                             // (outer, n, inner) dense
+    const A* h0; const A* h1;
+    A scale;
+    int64_t outer, inner, y0_os, y1_os;
+    int n, K, nt, start, dstep, ext;
+};
+
+template <typename T>
+struct WlCorr1dAdj {
+    typedef WlCorr1dAdjArgs<T> Args;
+    typedef typename WlAcc<T>::type A;
+    static const int kThreads = 256;
+    static const int kMinWaves = 1;
+    static WL_DEV A z(const Args& a, const T* p0, const T* p1, int e) {
+        A acc = 0;
+        for (int t = 0; t < a.nt; ++t) {
+            const int k = e - a.start - a.dstep * t;
+            if ((unsigned)k >= (unsigned)a.K) continue;
+            acc += a.h0[t] * (A)p0[(int64_t)k * a.inner];
+            if (p1) acc += a.h1[t] * (A)p1[(int64_t)k * a.inner];
+        }
+        return acc;
+    }
+    static WL_DEV void run(const Args& a, const WlCtx& ctx) {
+        const int64_t per = (int64_t)a.n * a.inner;
+        const int64_t idx = ctx.bid * kThreads + ctx.tid;
+        if (idx >= a.outer * per) return;
+        const int64_t o = idx / per;
+        const int64_t rem = idx - o * per;
+        const int m = (int)(rem / a.inner);
+        const int64_t i = rem - (int64_t)m * a.inner;
+        const T* p0 = a.y0 + o * a.y0_os + i;
+        const T* p1 = a.y1 ? a.y1 + o * a.y1_os + i : nullptr;
+        const int elo = a.start, ehi = a.start + a.K - 1 + a.dstep * (a.nt - 1);
+        // up to two progressions (first, step) up to ehi, or one run [first[0], last] of consecutive positions
+        int nf = 1, step = 0, first[2] = {m, 0}, last = m;
+        const int n = a.n;
+        switch (a.ext) {
+            case WL_EXT_PERIODIC: step = n; break;
+            case WL_EXT_SYM: step = 2 * n; first[1] = -1 - m; nf = 2; break;
+            case WL_EXT_REFL:
+                if (n == 1) { first[0] = elo; last = ehi; }
+                else { step = 2 * n - 2; first[1] = -m; nf = (m == 0 || m == n - 1) ? 1 : 2; }
+                break;
+            case WL_EXT_REPLICATE:
+                if (m == 0) first[0] = elo;
+                if (m == n - 1) last = ehi;
+                break;
+            default: break;   // zero: the sample itself
+        }
+        A acc = 0;
+        if (step) {
+            for (int f = 0; f < nf; ++f)
+                for (int e = elo + wl_pmod(first[f] - elo, step); e <= ehi; e += step) acc += z(a, p0, p1, e);
+        } else {
+            const int e0 = first[0] < elo ? elo : first[0], e1 = last > ehi ? ehi : last;
+            for (int e = e0; e <= e1; ++e) acc += z(a, p0, p1, e);
+        }
+        a.dx[idx] = (T)(a.scale * acc);
+    }
+};
+
 template <typename T>
 struct WlSynth1dArgs {
     typedef typename WlAcc<T>::type A;

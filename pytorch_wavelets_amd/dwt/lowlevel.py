@@ -483,51 +483,280 @@ _ATROUS_EXT = {'zero': ops.EXT_ZERO, 'constant': ops.EXT_ZERO, 'symmetric': ops.
                'periodic': ops.EXT_PERIODIC, 'replicate': ops.EXT_REPLICATE}
 
 
+def _atrous_geom(n, L, dilation):
+    """(K, start) of the a-trous bank along an axis of n samples: the output length and the extended position its first
+    output's first tap reads (reference dwt/lowlevel.py:175-223)."""
+    L2 = (L * dilation) // 2
+    return n + 2 * L2 - dilation - dilation * (L - 1), -(L2 - dilation)
+
+
+class AFB1DAtrous(Function):
+    """The a-trous bank along one axis as an autograd node: ``AFB1DAtrous.apply(x, h0, h1, ext, dim, dilation) -> (lo, hi)``.
+    Backward = the transpose of the dilated correlation under the extension rule (ops.corr1d_adj) - upstream gets it from
+    autograd through mypad + conv2d."""
+
+    @staticmethod
+    def forward(ctx, x, h0, h1, ext, dim, dilation):
+        ctx.save_for_backward(h0, h1)
+        ctx.geom = (ext, dim, dilation, x.shape[dim])
+        K, start = _atrous_geom(x.shape[dim], h0.numel(), dilation)
+        return ops.corr1d(x, dim, h0, h1, K, start, 1, dilation, ext)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dlo, dhi):
+        dx = None
+        if ctx.needs_input_grad[0]:
+            h0, h1 = ctx.saved_tensors
+            ext, dim, dilation, n = ctx.geom
+            dx = ops.corr1d_adj(dlo, dhi, dim, h0, h1, n, _atrous_geom(n, h0.numel(), dilation)[1], dilation, ext)
+        return dx, None, None, None, None, None
+
+
 def afb1d_atrous(x, h0, h1, mode='periodic', dim=-1, dilation=1):
     """Undecimated (a-trous) 1-D analysis along one axis (reference dwt/lowlevel.py:175-223): the taps are dilated, the
     signal is padded by (L*dilation)//2 - dilation before and (L*dilation)//2 after with `mode`, the output keeps the
-    input size.  Returns (N, 2C, H, W) with channel 2c = low.  NB like upstream the padding is done by ``mypad``, which
-    knows 'symmetric', 'periodic', 'constant', 'reflect', 'replicate' and 'zero' - 'periodization' raises."""
+    input size.  Returns (N, 2C, H, W) with channel 2c = low; differentiable in x.  NB like upstream the padding is done by
+    ``mypad``, which knows 'symmetric', 'periodic', 'constant', 'reflect', 'replicate' and 'zero' - 'periodization' raises."""
     if mode not in _ATROUS_EXT:
         raise ValueError("Unkown pad type: {}".format(mode))
-    d = dim % 4
-    t0, t1 = _as_taps(h0, x), _as_taps(h1, x)
-    L = t0.numel()
-    L2 = (L * dilation) // 2
-    n = x.shape[d]
-    K = n + 2 * L2 - dilation - dilation * (L - 1)
-    lo, hi = ops.corr1d(x, d, t0, t1, K, -(L2 - dilation), 1, dilation, _ATROUS_EXT[mode])
+    lo, hi = AFB1DAtrous.apply(x, _as_taps(h0, x), _as_taps(h1, x), _ATROUS_EXT[mode], dim % 4, dilation)
     nb, c = lo.shape[:2]
     return torch.stack([lo, hi], dim=2).reshape(nb, 2 * c, lo.shape[2], lo.shape[3])
 
 
-def afb2d_atrous(x, filts, mode='periodization', dilation=1):
-    """One undecimated 2-D level (reference dwt/lowlevel.py:475-521): rows then columns; returns (N, 4C, H, W) with
-    channel 4c + 2r + b (r: band along W, b: band along H), i.e. (ll, lh, hl, hh) per input channel."""
-    tensorize = [not isinstance(f, torch.Tensor) for f in filts]
-    if len(filts) == 2:
-        h0, h1 = filts
-        if True in tensorize:
-            h0_col, h1_col, h0_row, h1_row = prep_filt_afb2d(h0, h1, device=x.device)
-        else:
-            h0_col, h0_row, h1_col, h1_row = h0, h0.transpose(2, 3), h1, h1.transpose(2, 3)
-    elif len(filts) == 4:
-        if True in tensorize:
-            h0_col, h1_col, h0_row, h1_row = prep_filt_afb2d(*filts, device=x.device)
-        else:
-            h0_col, h1_col, h0_row, h1_row = filts
-    else:
-        raise ValueError("Unknown form for input filts")
-    if mode not in _ATROUS_EXT:
-        raise ValueError("Unkown pad type: {}".format(mode))
+def _atrous_level(x, t_row, t_col, ext, dilation):
+    """One undecimated 2-D level, no autograd: the fused kernel (csrc/wl_swt2d.h: x read once, the four sub-bands written once
+    in the returned layout), or the two single-axis passes for what it declines."""
     if FUSED_LEVELS and x.dim() == 4:
-        # one launch per level (csrc/wl_swt2d.h): x read once, the four sub-bands written once in the returned layout
-        y = ops.swt2d_level(x, _as_taps(h0_row, x), _as_taps(h1_row, x), _as_taps(h0_col, x), _as_taps(h1_col, x), dilation,
-                            _ATROUS_EXT[mode])
+        y = ops.swt2d_level(x, t_row[0], t_row[1], t_col[0], t_col[1], dilation, ext)
         if y is not None:
             return y
-    lohi = afb1d_atrous(x, h0_row, h1_row, mode=mode, dim=3, dilation=dilation)
-    return afb1d_atrous(lohi, h0_col, h1_col, mode=mode, dim=2, dilation=dilation)
+
+    def bank(v, taps, dim):
+        K, start = _atrous_geom(v.shape[dim], taps[0].numel(), dilation)
+        lo, hi = ops.corr1d(v, dim, taps[0], taps[1], K, start, 1, dilation, ext)
+        nb, c = lo.shape[:2]
+        return torch.stack([lo, hi], dim=2).reshape(nb, 2 * c, lo.shape[2], lo.shape[3])
+    return bank(bank(x, t_row, 3), t_col, 2)
+
+
+def _atrous_level_adj(y, ll, ll_mode, t_row, t_col, ext, dilation, scale, hw):
+    """scale * the transpose of _atrous_level: y (N,4C,Kh,Kw) or None -> (N,C,H,W), hw = (H, W); `ll` replaces (ll_mode 1) or is
+    added to (2) the channels 4c + 0.  One launch (csrc/wl_iswt2d.h), or three of the single-axis transpose for what the fused
+    kernel declines (mirror / replicate rules, dilated filters too long for its tile, odd L * dilation)."""
+    if FUSED_LEVELS:
+        x = ops.iswt2d_level(y, t_row[0], t_row[1], t_col[0], t_col[1], dilation, ext, scale, ll, ll_mode)
+        if x is not None:
+            return x
+    H, W = hw
+    sh = _atrous_geom(H, t_col[0].numel(), dilation)[1]
+    sw = _atrous_geom(W, t_row[0].numel(), dilation)[1]
+    u = []
+    for r in (0, 1):                         # along H: the two bands b of each band r along W
+        if y is None:
+            y0, y1 = (ll if r == 0 else None), None
+        else:
+            y0, y1 = y[:, 2 * r::4], y[:, 2 * r + 1::4]
+            if r == 0 and ll_mode == 1:
+                y0 = ll
+            elif r == 0 and ll_mode == 2:
+                y0 = y0 + ll
+        if y0 is None:
+            u.append(None)
+        else:
+            u.append(ops.corr1d_adj(y0, y1, 2, t_col[0], None if y1 is None else t_col[1], H, sh, dilation, ext))
+    if u[1] is None:
+        return ops.corr1d_adj(u[0], None, 3, t_row[0], None, W, sw, dilation, ext, scale)
+    return ops.corr1d_adj(u[0], u[1], 3, t_row[0], t_row[1], W, sw, dilation, ext, scale)
+
+
+class AFB2DAtrousMulti(Function):
+    """J undecimated 2-D levels as ONE autograd node: ``AFB2DAtrousMulti.apply(x, h0_row, h1_row, h0_col, h1_col, ext,
+    dilation, J) -> (y_1 .. y_J)``, level j on the ll channels of level j-1 (a strided view, no copy) with the taps dilated by
+    dilation * 2**(j-1).  Backward: one launch of the transposed level per level, coarsest first; the gradient that arrives
+    from level j+1 joins the user's gradient on the ll channels inside the kernel (no clone, no zeros_like), and a level whose
+    output nobody used contributes nothing but what comes through its ll channels."""
+
+    @staticmethod
+    def forward(ctx, x, h0_row, h1_row, h0_col, h1_col, ext, dilation, J):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(h0_row, h1_row, h0_col, h1_col)
+        outs, hws, ll = [], [], x
+        for j in range(J):
+            hws.append(tuple(ll.shape[-2:]))
+            y = _atrous_level(ll, (h0_row, h1_row), (h0_col, h1_col), ext, dilation * 2 ** j)
+            outs.append(y)
+            ll = y[:, 0::4]
+        ctx.geom = (ext, dilation, hws)
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *dys):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 8
+        h0_row, h1_row, h0_col, h1_col = ctx.saved_tensors
+        ext, dilation, hws = ctx.geom
+        carry = None
+        for j in range(len(dys) - 1, -1, -1):
+            dy = dys[j]
+            if dy is None and carry is None:
+                continue
+            ll_mode = 0 if carry is None else (1 if dy is None else 2)
+            carry = _atrous_level_adj(dy, carry, ll_mode, (h0_row, h1_row), (h0_col, h1_col), ext, dilation * 2 ** j, 1.0, hws[j])
+        return (carry,) + (None,) * 7
+
+
+def _atrous_filts(filts, ref, prep):
+    """The reference's 2- / 4-tuple of filters (arrays or prepared tensors) -> (col lo, col hi, row lo, row hi)."""
+    tensorize = [not isinstance(f, torch.Tensor) for f in filts]
+    if len(filts) == 2:
+        f0, f1 = filts
+        if True in tensorize:
+            return prep(f0, f1, device=ref.device)
+        return f0, f1, f0.transpose(2, 3), f1.transpose(2, 3)
+    if len(filts) == 4:
+        if True in tensorize:
+            return prep(*filts, device=ref.device)
+        return tuple(filts)
+    raise ValueError("Unknown form for input filts")
+
+
+def afb2d_atrous_multi(x, filts, mode, dilation, J):
+    """J undecimated levels (SWTForward.forward's loop): a list of (N, 4C, H, W), level j+1 on the ll channels of level j with
+    the taps dilated twice as far; differentiable in x."""
+    h0_col, h1_col, h0_row, h1_row = _atrous_filts(filts, x, prep_filt_afb2d)
+    if mode not in _ATROUS_EXT:
+        raise ValueError("Unkown pad type: {}".format(mode))
+    if J < 1:
+        return []
+    return list(AFB2DAtrousMulti.apply(x, _as_taps(h0_row, x), _as_taps(h1_row, x), _as_taps(h0_col, x), _as_taps(h1_col, x),
+                                       _ATROUS_EXT[mode], dilation, J))
+
+
+def afb2d_atrous(x, filts, mode='periodization', dilation=1):
+    """One undecimated 2-D level (reference dwt/lowlevel.py:475-521): rows then columns; returns (N, 4C, H, W) with
+    channel 4c + 2r + b (r: band along W, b: band along H), i.e. (ll, lh, hl, hh) per input channel.  Differentiable in x (one
+    launch of the transposed level, csrc/wl_iswt2d.h)."""
+    return afb2d_atrous_multi(x, filts, mode, dilation, 1)[0]
+
+
+# ---- the way back: the transposed a-trous bank with the synthesis taps ------------------------------------------------------
+# Upstream's dwt/swt_inverse.py is dead code (no imports; its forward calls the decimated sfb2d; its sfb1d_atrous divides by
+# 2 * dilation), so the inverse is defined here by its mathematics.  With A_b(g, periodic, d) the n x n matrix of afb1d_atrous for
+# the stored synthesis taps g_b (pywt's rec_lo / rec_hi, as prep_filt_sfb2d stores them) and B_b the same for the analysis taps,
+#     1/2 (A_0(g)^T B_0 + A_1(g)^T B_1) = I        for every pywt wavelet, even tap count and dilation,
+# i.e. per axis x = 1/2 (A_0(g)^T lo + A_1(g)^T hi), per 2-D level 1/4 of the four-band sum.  In the other pad modes the forward
+# keeps n samples and loses what the border needs: 'periodic' only.
+def _check_atrous_inverse(mode, *taps):
+    if mode != 'periodic':
+        raise ValueError("the inverse stationary transform is defined for mode 'periodic' only, not {!r}".format(mode))
+    for t in taps:
+        if t.numel() % 2:
+            raise ValueError("the inverse stationary transform needs an even number of taps, not {}".format(t.numel()))
+
+
+def _as_syn_taps(g, ref):
+    """Array-likes are used as given (no reversal), like sfb1d / sfb2d; tensors are taken as already prepared."""
+    if isinstance(g, torch.Tensor):
+        return g
+    return torch.tensor(np.copy(np.array(g, dtype=np.float64).ravel()), dtype=torch.float, device=ref.device)
+
+
+class SFB1DAtrous(Function):
+    """``SFB1DAtrous.apply(lo, hi, g0, g1, dim, dilation) -> x = 1/2 (A_0(g)^T lo + A_1(g)^T hi)``, periodic; backward = 1/2 of
+    the a-trous analysis with the synthesis taps."""
+
+    @staticmethod
+    def forward(ctx, lo, hi, g0, g1, dim, dilation):
+        ctx.save_for_backward(g0, g1)
+        ctx.geom = (dim, dilation)
+        n = lo.shape[dim]
+        return ops.corr1d_adj(lo, hi, dim, g0, g1, n, _atrous_geom(n, g0.numel(), dilation)[1], dilation, ops.EXT_PERIODIC, 0.5)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dx):
+        g0, g1 = ctx.saved_tensors
+        dim, dilation = ctx.geom
+        K, start = _atrous_geom(dx.shape[dim], g0.numel(), dilation)
+        dlo, dhi = ops.corr1d(dx, dim, g0, g1, K, start, 1, dilation, ops.EXT_PERIODIC)
+        return dlo.mul_(0.5), dhi.mul_(0.5), None, None, None, None
+
+
+def sfb1d_atrous(lo, hi, g0, g1, mode='periodic', dim=-1, dilation=1):
+    """The inverse of afb1d_atrous along one axis of 4-D tensors: x = 1/2 (A_0(g)^T lo + A_1(g)^T hi), A_b(g) the a-trous
+    analysis matrix of the synthesis taps (arrays are used as given, like sfb1d).  Upstream's sketch of this function
+    (dwt/swt_inverse.py) pads, runs conv_transpose2d and divides by 2*dilation, and was never run; this one inverts
+    afb1d_atrous exactly in 'periodic' mode and raises ValueError in every other."""
+    t0, t1 = _as_syn_taps(g0, lo), _as_syn_taps(g1, lo)
+    _check_atrous_inverse(mode, t0, t1)
+    if lo.shape != hi.shape:
+        raise ValueError("lo is {} and hi is {}".format(tuple(lo.shape), tuple(hi.shape)))
+    return SFB1DAtrous.apply(lo, hi, t0, t1, dim % lo.dim(), dilation)
+
+
+class SWTInvMulti(Function):
+    """All levels of the inverse stationary transform as ONE autograd node: ``SWTInvMulti.apply(g0_row, g1_row, g0_col, g1_col,
+    dilation, *coeffs) -> x`` with coeffs[j] (N,4C,H,W), finest first, level j dilated by dilation * 2**j.  It starts from the ll
+    channels of the last entry; the ll channels of the finer entries are redundant and ignored (the reconstructed ll of the
+    coarser level takes their place inside the kernel).  Backward = 1/4 of the a-trous analysis (csrc/wl_swt2d.h) with the
+    synthesis taps, level by level."""
+
+    @staticmethod
+    def forward(ctx, g0_row, g1_row, g0_col, g1_col, dilation, *coeffs):
+        ctx.save_for_backward(g0_row, g1_row, g0_col, g1_col)
+        ctx.geom = (dilation, len(coeffs))
+        ctx.needs = [ctx.needs_input_grad[5 + j] for j in range(len(coeffs))]
+        ll = None
+        for j in range(len(coeffs) - 1, -1, -1):
+            ll = _atrous_level_adj(coeffs[j], ll, 0 if ll is None else 1, (g0_row, g1_row), (g0_col, g1_col), ops.EXT_PERIODIC,
+                                   dilation * 2 ** j, 0.25, tuple(coeffs[j].shape[-2:]))
+        return ll
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dx):
+        g0_row, g1_row, g0_col, g1_col = ctx.saved_tensors
+        dilation, J = ctx.geom
+        grads, cur = [], dx
+        for j in range(J):
+            if not any(ctx.needs[j:]):
+                break
+            g = _atrous_level(cur, (g0_row, g1_row), (g0_col, g1_col), ops.EXT_PERIODIC, dilation * 2 ** j).mul_(0.25)
+            grads.append(g)
+            cur = g[:, 0::4]
+        for g in grads[:J - 1]:
+            g[:, 0::4].zero_()                  # the ll channels of the finer levels were not read
+        grads = [g if ctx.needs[j] else None for j, g in enumerate(grads)] + [None] * (J - len(grads))
+        return (None,) * 5 + tuple(grads)
+
+
+def _swt_inverse(coeffs, taps, dilation=1):
+    coeffs = list(coeffs)
+    if len(coeffs) == 0:
+        raise ValueError("no coefficients: SWTInverse takes the list SWTForward returns")
+    shape = tuple(coeffs[0].shape)
+    if len(shape) != 4 or shape[1] % 4:
+        raise ValueError("a level is (N, 4C, H, W), not {}".format(shape))
+    for c in coeffs[1:]:
+        if tuple(c.shape) != shape or c.dtype != coeffs[0].dtype:
+            raise ValueError("the levels differ: {} {} and {} {}".format(shape, coeffs[0].dtype, tuple(c.shape), c.dtype))
+    g0_col, g1_col, g0_row, g1_row = taps
+    return SWTInvMulti.apply(g0_row, g1_row, g0_col, g1_col, dilation, *coeffs)
+
+
+def sfb2d_atrous(ll, lh, hl, hh, filts, mode='periodic', dilation=1):
+    """The inverse of afb2d_atrous: the four sub-bands (N, C, H, W) of one level -> x (N, C, H, W), 1/4 of the transposed a-trous
+    bank of the synthesis filters (``filts`` as for sfb2d: (g0_col, g1_col[, g0_row, g1_row]), arrays as given).  'periodic'
+    only: ValueError for any other mode."""
+    g0_col, g1_col, g0_row, g1_row = _atrous_filts(filts, ll, prep_filt_sfb2d)
+    taps = tuple(_as_syn_taps(g, ll) for g in (g0_col, g1_col, g0_row, g1_row))
+    _check_atrous_inverse(mode, *taps)
+    n, c = ll.shape[:2]
+    y = torch.stack([ll, lh, hl, hh], dim=2).reshape(n, 4 * c, ll.shape[2], ll.shape[3])
+    return _swt_inverse([y], taps, dilation)
 
 
 def prep_filt_afb2d_nonsep(h0_col, h1_col, h0_row=None, h1_row=None, device=None):

@@ -119,11 +119,35 @@ class SWTForward(nn.Module):
         self.mode = mode
 
     def forward(self, x):
-        ll = x
-        coeffs = []
+        # all J levels are one autograd node; its backward is one launch of the transposed level per level (csrc/wl_iswt2d.h)
         filts = (self.h0_col, self.h1_col, self.h0_row, self.h1_row)
-        for j in range(self.J):
-            y = lowlevel.afb2d_atrous(ll, filts, self.mode, 2 ** j)
-            coeffs.append(y)
-            ll = y[:, 0::4]
-        return coeffs
+        return lowlevel.afb2d_atrous_multi(x, filts, self.mode, 1, self.J)
+
+
+class SWTInverse(nn.Module):
+    """Inverse of :class:`SWTForward`: ``SWTInverse(wave='db1', mode='periodic')(coeffs) -> x`` takes the list SWTForward
+    returns (J tensors (N, 4C, H, W), finest first) and returns (N, C, H, W).  It starts from the ll channels of the last
+    entry and runs one fused launch per level, coarsest first, with the filters dilated by 2**j; the ll channels of the finer
+    entries are redundant and ignored.  Differentiable in the coefficients.
+
+    Upstream's ``dwt/swt_inverse.py`` is an unfinished sketch (no imports, it calls the decimated ``sfb2d``), so this module is
+    defined by its mathematics and deviates from that sketch on purpose: per axis x = 1/2 (A_0(g)^T lo + A_1(g)^T hi), where
+    A_b(g) is the matrix of the a-trous analysis (``afb1d_atrous``) run with the stored synthesis taps - 1/4 per 2-D level, not
+    upstream's ``/(2*dilation)``; ``mode='periodic'`` only (in the other pad modes the forward keeps n samples and loses what
+    the borders need: ValueError); no ``separable`` argument; even tap counts only (ValueError)."""
+
+    def __init__(self, wave='db1', mode='periodic'):
+        super().__init__()
+        g0_col, g1_col, g0_row, g1_row = _resolve_bank(wave, 'rec_lo', 'rec_hi')
+        filts = lowlevel.prep_filt_sfb2d(g0_col, g1_col, g0_row, g1_row)
+        lowlevel._check_atrous_inverse(mode, *filts)
+        self.register_buffer('g0_col', filts[0])
+        self.register_buffer('g1_col', filts[1])
+        self.register_buffer('g0_row', filts[2])
+        self.register_buffer('g1_row', filts[3])
+        self.mode = mode
+
+    def forward(self, coeffs):
+        taps = (self.g0_col, self.g1_col, self.g0_row, self.g1_row)
+        lowlevel._check_atrous_inverse(self.mode, *taps)
+        return lowlevel._swt_inverse(coeffs, taps)

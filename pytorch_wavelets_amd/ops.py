@@ -890,6 +890,126 @@ def swt2d_level(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, dilation, ext):
     return y
 
 
+def iswt2d_level(y, h_w_lo, h_w_hi, h_h_lo, h_h_hi, dilation, ext, scale=1.0, ll=None, ll_mode=0):
+    """The transpose of swt2d_level in ONE launch (wl_iswt2d_level): y (N,4C,H,W), channel 4c + 2r + b -> (N,C,H,W),
+    scale * sum_{r,b} A_r^T A_b^T y[:, 2r+b::4] with the same taps, dilation and `ext` as the analysis.  scale 1 = the backward of
+    a level; scale 1/4 with the synthesis taps and EXT_PERIODIC = one level of the inverse.  `ll` (N,C,H,W) - dense, or
+    uniformly spaced planes of dense rows such as `y[:, 0::4]` of another level - with ll_mode 1 replaces the channels 4c + 0
+    (y may then be None: the other bands are zeros), with ll_mode 2 is added to them.  y is read dense: a strided or expanded
+    tensor (the cotangent of a `.sum()`, say) is copied once first.  None when the kernel does not cover the configuration
+    (callers chain corr1d_adj)."""
+    ref = y if y is not None else ll
+    _check_tensor(ref, 'y')
+    if (ll is None) != (ll_mode == 0) or (y is None and ll_mode != 1):
+        raise ValueError('iswt2d_level: ll_mode %d does not go with the tensors given' % ll_mode)
+    if y is not None:
+        N, C4, H, W = y.shape
+        if C4 % 4:
+            raise ValueError('iswt2d_level: y has %d channels, not four sub-bands per input channel' % C4)
+        C = C4 // 4
+        y = y.contiguous()
+    else:
+        N, C, H, W = ll.shape
+    ll_ps = 0
+    if ll is not None:
+        _same_device(y, ll)
+        if tuple(ll.shape) != (N, C, H, W) or ll.dtype != ref.dtype:
+            raise ValueError('iswt2d_level: ll is %s %s, expected %s %s' % (tuple(ll.shape), ll.dtype, (N, C, H, W), ref.dtype))
+        st = None if ll.numel() == 0 else _plane_strides(ll)
+        if st is None or st[1] != W:
+            ll = ll.contiguous()
+            st = (H * W, W)
+        ll_ps = st[0]
+    Lw, Lh = h_w_lo.numel(), h_h_lo.numel()
+    if h_w_hi.numel() != Lw or h_h_hi.numel() != Lh or ref.numel() == 0:
+        return None
+    key = ('iswt2d', ref.device, ref.dtype, N * C, H, W, y is None, ll_ps, ll_mode, Lw, Lh, dilation, ext)
+    if key in _FUSED_DECLINED:
+        return None
+    taps = [_taps(h, ref) for h in (h_w_lo, h_w_hi, h_h_lo, h_h_hi)]
+    x = torch.empty((N, C, H, W), dtype=ref.dtype, device=ref.device)
+    rc = _call('wl_iswt2d_level', ref, None if y is None else y.data_ptr(), 4 * H * W, None if ll is None else ll.data_ptr(), ll_ps,
+               ll_mode, x.data_ptr(), _DTYPES[ref.dtype], N * C, H, W, taps[0].data_ptr(), taps[1].data_ptr(), taps[2].data_ptr(),
+               taps[3].data_ptr(), Lw, Lh, dilation, ext, float(scale), _stream(ref))
+    if rc == -3:
+        _remember_decline(key)
+        return None
+    _lib.check(rc, 'wl_iswt2d_level')
+    return x
+
+
+def _outer_stride(t, dim):
+    """Outer stride (elements) of t seen as (outer, K, inner) around axis `dim`: the axes from `dim` on packed, the axes before
+    it one uniformly spaced index (every 4th channel of a level, say) - or None when t has no such description."""
+    shape, st = t.shape, t.stride()
+    inner = 1
+    for k in range(t.dim() - 1, dim - 1, -1):
+        if shape[k] > 1 and st[k] != inner:
+            return None
+        inner *= shape[k]
+    os_, span = None, 1
+    for k in range(dim - 1, -1, -1):
+        if shape[k] == 1:
+            continue
+        if os_ is None:
+            os_ = st[k]
+            if os_ < inner:
+                return None
+        elif st[k] != os_ * span:
+            return None
+        span *= shape[k]
+    return inner if os_ is None else os_
+
+
+def _with_outer_stride(t, dim):
+    """(t, outer stride) for the single-axis kernels - t itself where it has such a description, a dense copy otherwise;
+    (None, 0) for None."""
+    if t is None:
+        return None, 0
+    os_ = _outer_stride(t, dim) if t.numel() else None
+    if os_ is None:
+        t = t.contiguous()
+        os_ = _outer_stride(t, dim) if t.numel() else 0
+    return t, os_
+
+
+def corr1d_adj(y0, y1, dim, h0, h1, n, start, tap_step=1, ext=EXT_SYM, scale=1.0):
+    """The transpose of corr1d with step 1 (wl_corr1d_adj): y0 / y1 (same shape, K samples along `dim`; y1 / h1 may be None) ->
+    dx with n samples along `dim`, dx = scale * (A_0^T y0 + A_1^T y1) where A_b x = sum_t h_b[t] * ext(x, start + k + tap_step*t).
+    Every extension rule but the periodizations, pads of any length.  The inputs may be uniformly spaced along the axes before
+    `dim` (no copy of every 4th channel of a level)."""
+    _check_tensor(y0, 'y0')
+    if ext not in (EXT_ZERO, EXT_SYM, EXT_REFL, EXT_PERIODIC, EXT_REPLICATE):
+        raise ValueError('corr1d_adj: extension %r has no transpose here' % (ext,))
+    if (y1 is None) != (h1 is None):
+        raise ValueError('corr1d_adj: y1 and h1 go together')
+    dim = dim % y0.dim()
+    if y1 is not None:
+        _same_device(y0, y1)
+        if y1.shape != y0.shape or y1.dtype != y0.dtype:
+            raise ValueError('corr1d_adj: y0 is %s %s, y1 is %s %s' % (tuple(y0.shape), y0.dtype, tuple(y1.shape), y1.dtype))
+    y0, os0 = _with_outer_stride(y0, dim)
+    y1, os1 = _with_outer_stride(y1, dim)
+    K = y0.shape[dim]
+    outer = 1
+    for v in y0.shape[:dim]:
+        outer *= v
+    inner = 1
+    for v in y0.shape[dim + 1:]:
+        inner *= v
+    t0 = _taps(h0, y0)
+    t1 = None if h1 is None else _taps(h1, y0)
+    shape = list(y0.shape)
+    shape[dim] = n
+    dx = torch.empty(shape, dtype=y0.dtype, device=y0.device)
+    if dx.numel():
+        rc = _call('wl_corr1d_adj', y0, y0.data_ptr(), os0, None if y1 is None else y1.data_ptr(), os1, dx.data_ptr(),
+                   _DTYPES[y0.dtype], outer, n, inner, K, t0.data_ptr(), None if t1 is None else t1.data_ptr(), t0.numel(), start,
+                   tap_step, ext, float(scale), _stream(y0))
+        _lib.check(rc, 'wl_corr1d_adj')
+    return dx
+
+
 def sfb1d_fused(lo, his, g0, g1, mode, out_len=None):
     """All len(his) (1..4) synthesis levels along the LAST axis in ONE launch (wl_dwt1d_synthesis_fused): lo (..., n_lo), his =
     [finest .. coarsest] (None = zeros) -> y (..., out_len) (default: the full reconstruction 2 n_hi[0] - L + 2), or None when
