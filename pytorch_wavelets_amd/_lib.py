@@ -28,12 +28,15 @@ def get():
     return _LIB
 
 
+WL_ERR_UNSUPPORTED = -3   # a launcher declines the configuration (include/wavelets_hip.h): the callers in ops.py take another kernel
+
+
 def check(rc, what):
     if rc == 0:
         return
-    names = {-1: 'WL_ERR_MODE', -2: 'WL_ERR_SHAPE', -3: 'WL_ERR_UNSUPPORTED', -4: 'WL_ERR_DTYPE',
+    names = {-1: 'WL_ERR_MODE', -2: 'WL_ERR_SHAPE', WL_ERR_UNSUPPORTED: 'WL_ERR_UNSUPPORTED', -4: 'WL_ERR_DTYPE',
              -5: 'WL_ERR_TAPS'}
-    if rc == -3:
+    if rc == WL_ERR_UNSUPPORTED:
         raise NotImplementedError('%s: configuration not supported by the gfx950 engine '
                                   '(WL_ERR_UNSUPPORTED)' % what)
     raise RuntimeError('%s failed: %s' % (what, names.get(rc, 'hipError_t %d' % rc)))

@@ -15,7 +15,7 @@ _MODE_TO_INT = {'zero': 0, 'symmetric': 1, 'per': 2, 'periodization': 2, 'consta
 _INT_TO_MODE = {0: 'zero', 1: 'symmetric', 2: 'periodization', 3: 'constant', 4: 'reflect',
                 5: 'replicate', 6: 'periodic'}
 FUSED_LEVELS = True   # set False to force one launch per level (A/B measurements)
-WIDE_ONE_LEVEL = 640  # coefficient-row pairs: a synthesis level left on its own whose output is at least this wide goes to the one-level strip kernel (SFB2DMulti.forward)
+WIDE_ONE_LEVEL = 640  # coefficient-row pairs: a synthesis level left on its own whose output is at least this wide goes to the one-level strip kernel (_synthesis_ladder)
 _FILTERBANK_MODES = (0, 1, 2, 4, 6)   # the ones afb1d/sfb1d accept upstream (dwt/lowlevel.py:134-170)
 
 
@@ -90,6 +90,66 @@ class SFB2D(Function):
         return dlow, dhigh, None, None, None, None, None
 
 
+def _synthesis_ladder(ll, highs, banks, mode, out_hws=None):
+    """All synthesis levels in as few launches as the engine takes: ll = the coarsest low-pass, highs finest first (``None`` =
+    zeros), banks = (g0_row, g1_row, g0_col, g1_col) as the ops calls take them -> (x, ll_shapes), ll_shapes[j] = the size of
+    the low-pass handed to level j before its 'unpad'.  The inverse transform (SFB2DMulti.forward) and the backward of the
+    analysis (AFB2DMulti._backward, with the analysis taps) both run it: there out_hws[j] is the input size of level j, to which
+    its output is cropped - by the kernel on the one-level paths, as a view after a multi-level launch -, while the inverse
+    leaves a surplus row / column to the next level's 'unpad'."""
+    J, L = len(highs), banks[0].numel()
+    ll_shapes = [None] * J
+    j = J - 1
+    while j >= 0:
+        n = 0                       # levels j, j-1, .. that one launch can take together: a missing level ends the group
+        while n < 4 and j - n >= 0 and highs[j - n] is not None:
+            n += 1
+        # small planes (CNN feature maps): several planes per workgroup, up to four levels in LDS
+        res = ops.sfb2d_small(ll, list(highs[j - n + 1:j + 1]), *banks, mode) if FUSED_LEVELS and n else None
+        if res is None and n:
+            # More levels than one streaming launch takes (three): the COARSEST (j mod 3) + 1 go first, so that the finest -
+            # nearly all of the bytes - go three to a launch (J = 4 as 3 + 1 from the coarse end ran its finest level
+            # alone: 0.288 ms against 0.188 for J = 3 at 128 x 3 x 512 x 512); the coarse remainder are small planes.
+            m = min(n, 3, (j % 3) + 1 if j + 1 > 3 else 3)
+            if FUSED_LEVELS and m < n:
+                res = ops.sfb2d_small(ll, list(highs[j - m + 1:j + 1]), *banks, mode)
+            n = m
+        while FUSED_LEVELS and n >= 1 and res is None:
+            if n == 1 and 2 * highs[j].shape[-1] >= WIDE_ONE_LEVEL:
+                # a single WIDE level: the one-level strip kernel is ahead of the fused kernel's one-level form (same-box, float32,
+                # tools/gpu_r5u.py: 64x3x1024^2 0.333 -> 0.309 ms, 128x3x768^2 0.362 -> 0.342, 128x3x640^2 0.244 -> 0.228);
+                # when it declines (few planes, a width that is no multiple of four) the fused kernel is asked as before
+                # (the reference's 'unpad' drops exactly ONE surplus row / column, dwt/transform2d.py:141-146: a low-pass that is
+                # larger than that is malformed and takes the per-level path below, which raises like every other path)
+                h = highs[j]
+                dh, dw = ll.shape[-2] - h.shape[-2], ll.shape[-1] - h.shape[-1]
+                if 0 <= dh <= 1 and 0 <= dw <= 1:
+                    res = ops.sfb2d_stream(ll[..., :h.shape[-2], :h.shape[-1]], h, *banks, mode,
+                                           out_hw=None if out_hws is None else out_hws[j], force=ops.STREAM_FORCE)
+            if res is None:
+                res = ops.sfb2d_fused(ll, list(highs[j - n + 1:j + 1]), *banks, mode)
+            if res is None:
+                n -= 1
+        if res is not None:
+            sh = tuple(ll.shape[-2:])
+            for i in range(j, j - n, -1):
+                ll_shapes[i] = sh
+                sh = tuple(ops.synth_len(k, L, mode) for k in highs[i].shape[-2:])
+            j -= n
+            ll = res if out_hws is None else res[..., :out_hws[j + 1][0], :out_hws[j + 1][1]]
+            continue
+        h = highs[j]
+        ll_shapes[j] = tuple(ll.shape[-2:])
+        if h is not None:
+            if ll.shape[-2] > h.shape[-2]:
+                ll = ll[..., :-1, :]
+            if ll.shape[-1] > h.shape[-1]:
+                ll = ll[..., :-1]
+        ll = ops.sfb2d_best(ll, h, *banks, mode, out_hw=None if out_hws is None else out_hws[j])
+        j -= 1
+    return ll, ll_shapes
+
+
 class SFB2DMulti(Function):
     """All synthesis levels as ONE autograd node: ``SFB2DMulti.apply(yl, g0_row, g1_row, g0_col, g1_col, mode_int,
     *yh) -> x`` with yh finest first, ``None`` entries = zeros (the level loop of DWTInverse.forward, reference
@@ -107,65 +167,8 @@ class SFB2DMulti(Function):
         ctx.mode = mode
         ctx.hints = ops.current_hints()     # (the module's kernel-variant hints, re-installed around the backward pass: autograd's thread)
         ctx.has_highs = [h is not None for h in yh]
-        J = len(yh)
-        ll_shapes = [None] * J          # the low-pass handed to level j, before the 'unpad'
-        ll, j = yl, J - 1
-        while j >= 0:
-            n = 0                       # levels j, j-1, .. that one launch can take together
-            while n < 4 and j - n >= 0 and yh[j - n] is not None:
-                n += 1
-            # small planes (CNN feature maps): several planes per workgroup, up to four levels in LDS
-            res = ops.sfb2d_small(ll, list(yh[j - n + 1:j + 1]), g0_row, g1_row, g0_col, g1_col, mode) if FUSED_LEVELS and n else None
-            if res is None and n:
-                # More levels than one streaming launch takes (three): the COARSEST (j mod 3) + 1 go first, so that the finest -
-                # nearly all of the bytes - go three to a launch (J = 4 as 3 + 1 from the coarse end ran its finest level
-                # alone: 0.288 ms against 0.188 for J = 3 at 128 x 3 x 512 x 512); the coarse remainder are small planes.
-                m = min(n, 3, (j % 3) + 1 if j + 1 > 3 else 3)
-                if FUSED_LEVELS and m < n:
-                    res = ops.sfb2d_small(ll, list(yh[j - m + 1:j + 1]), g0_row, g1_row, g0_col, g1_col, mode)
-                n = m
-            took_strip = False
-            while FUSED_LEVELS and n >= 1 and res is None:
-                if n == 1 and 2 * yh[j].shape[-1] >= WIDE_ONE_LEVEL:
-                    # a single WIDE level: the one-level strip kernel is ahead of the fused kernel's one-level form (same-box, float32,
-                    # tools/gpu_r5u.py: 64x3x1024^2 0.333 -> 0.309 ms, 128x3x768^2 0.362 -> 0.342, 128x3x640^2 0.244 -> 0.228);
-                    # when it declines (few planes, a width that is no multiple of four) the fused kernel is asked as before
-                    # (the reference's 'unpad' drops exactly ONE surplus row / column, dwt/transform2d.py:141-146: a low-pass that is
-                    # larger than that is malformed and takes the per-level path below, which raises like every other path)
-                    h = yh[j]
-                    dh, dw = ll.shape[-2] - h.shape[-2], ll.shape[-1] - h.shape[-1]
-                    lc = ll[..., :h.shape[-2], :h.shape[-1]]
-                    one = (ops.sfb2d_stream(lc, h, g0_row, g1_row, g0_col, g1_col, mode, force=ops.STREAM_FORCE)
-                           if 0 <= dh <= 1 and 0 <= dw <= 1 else None)
-                    if one is not None:
-                        ll_shapes[j] = tuple(ll.shape[-2:])
-                        ll, j, took_strip = one, j - 1, True
-                        break
-                res = ops.sfb2d_fused(ll, list(yh[j - n + 1:j + 1]), g0_row, g1_row, g0_col, g1_col, mode)
-                if res is None:
-                    n -= 1
-            if took_strip:
-                continue
-            if res is not None:
-                L = g0_row.numel()
-                sh = tuple(ll.shape[-2:])
-                for i in range(j, j - n, -1):
-                    ll_shapes[i] = sh
-                    sh = ((2 * yh[i].shape[-2], 2 * yh[i].shape[-1]) if mode == 2
-                          else (2 * yh[i].shape[-2] - L + 2, 2 * yh[i].shape[-1] - L + 2))
-                ll, j = res, j - n
-                continue
-            h = yh[j]
-            ll_shapes[j] = tuple(ll.shape[-2:])
-            if h is not None:
-                if ll.shape[-2] > h.shape[-2]:
-                    ll = ll[..., :-1, :]
-                if ll.shape[-1] > h.shape[-1]:
-                    ll = ll[..., :-1]
-            ll = ops.sfb2d_best(ll, h, g0_row, g1_row, g0_col, g1_col, mode)
-            j -= 1
-        ctx.ll_shapes = ll_shapes
-        return ll
+        x, ctx.ll_shapes = _synthesis_ladder(yl, yh, (g0_row, g1_row, g0_col, g1_col), mode)
+        return x
 
     @staticmethod
     @once_differentiable
@@ -269,46 +272,9 @@ class AFB2DMulti(Function):
     def _backward(ctx, dyl, *dyh):
         dx = None
         if ctx.needs_input_grad[0]:
-            h0_row, h1_row, h0_col, h1_col = ctx.saved_tensors
-            dx, j = dyl, len(dyh) - 1
-            while j >= 0:
-                # the crop to the input size of each level is the 'unpad' of the inverse transform: up to three levels
-                # in one launch of the streaming synthesis kernel, the last crop as a view
-                n = min(4, j + 1)
-                grp = list(dyh[j - n + 1:j + 1])
-                res = (ops.sfb2d_small(dx, grp, h0_row, h1_row, h0_col, h1_col, ctx.mode)
-                       if FUSED_LEVELS and all(g is not None for g in grp) else None)
-                if res is None:
-                    # the coarsest (j mod 3) + 1 levels first, so that the finest go three to a launch (see SFB2DMulti.forward)
-                    n = min(3, j + 1, (j % 3) + 1 if j + 1 > 3 else 3)
-                    if FUSED_LEVELS and n < min(4, j + 1):
-                        grp = list(dyh[j - n + 1:j + 1])
-                        if all(g is not None for g in grp):
-                            res = ops.sfb2d_small(dx, grp, h0_row, h1_row, h0_col, h1_col, ctx.mode)
-                took_strip = False
-                while FUSED_LEVELS and n >= 1 and res is None:
-                    grp = list(dyh[j - n + 1:j + 1])
-                    ok = all(g is not None for g in grp)
-                    if ok and n == 1 and 2 * grp[0].shape[-1] >= WIDE_ONE_LEVEL:
-                        # a single wide level: the strip kernel first (SFB2DMulti.forward has the measurements)
-                        one = ops.sfb2d_stream(dx, grp[0], h0_row, h1_row, h0_col, h1_col, ctx.mode, out_hw=ctx.shapes[j], force=ops.STREAM_FORCE)
-                        if one is not None:
-                            dx, j, took_strip = one, j - 1, True
-                            break
-                    res = ops.sfb2d_fused(dx, grp, h0_row, h1_row, h0_col, h1_col, ctx.mode) if ok else None
-                    if res is None:
-                        n -= 1
-                if took_strip:
-                    continue
-                if res is not None:
-                    j -= n
-                    H, W = ctx.shapes[j + 1]
-                    dx = res[..., :H, :W]
-                    continue
-                dx = ops.sfb2d_best(dx, dyh[j], h0_row, h1_row, h0_col, h1_col, ctx.mode, out_hw=ctx.shapes[j])
-                j -= 1
-            if not dx.is_contiguous():
-                dx = dx.contiguous()
+            # an inverse transform with the analysis taps: the crop of each level to its input size is the inverse's 'unpad'
+            dx, _ = _synthesis_ladder(dyl, dyh, ctx.saved_tensors, ctx.mode, out_hws=ctx.shapes)
+            dx = dx.contiguous()             # (the crop after a multi-level launch is a view)
         return dx, None, None, None, None, None, None
 
 
@@ -392,11 +358,10 @@ class SFB1DMulti(Function):
         if FUSED_LEVELS and 1 <= J <= 4 and all(ctx.has_highs):
             res = ops.sfb1d_fused(x0, list(highs), g0, g1, mode)
             if res is not None:
-                L = g0.numel()
                 n = x0.shape[-1]
                 for j in range(J - 1, -1, -1):
                     lo_lens[j] = n
-                    n = 2 * highs[j].shape[-1] - L + 2
+                    n = ops.synth_len(highs[j].shape[-1], g0.numel(), mode)
         if res is None:
             res = x0
             for j in range(J - 1, -1, -1):

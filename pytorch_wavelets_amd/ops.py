@@ -72,6 +72,41 @@ def coeff_len(n, L, mode):
     return (n + 1) // 2 if mode == 2 else (n + L - 1) // 2
 
 
+def synth_len(K, L, mode, crop=None):
+    """Samples one synthesis level makes of K coefficients along an axis; `crop` (the analysis backward's input size) caps it."""
+    n = 2 * K if mode == 2 else 2 * K - L + 2
+    return n if crop is None else min(n, crop)
+
+
+def _synth_hw(Kh, Kw, Lh, Lw, mode, out_hw=None):
+    """synth_len along H and W; out_hw = the (H, W) crop or None."""
+    crop_h, crop_w = (out_hw[0], out_hw[1]) if out_hw is not None else (None, None)
+    return synth_len(Kh, Lh, mode, crop_h), synth_len(Kw, Lw, mode, crop_w)
+
+
+def _outer_inner(shape, dim):
+    """A dense tensor seen as (outer, shape[dim], inner)."""
+    outer = inner = 1
+    for v in shape[:dim]:
+        outer *= v
+    for v in shape[dim + 1:]:
+        inner *= v
+    return outer, inner
+
+
+def _new_pyramid(x, nlev, L, mode, axes):
+    """Uninitialised outputs of `nlev` analysis levels along the last `axes` (2: three bands per level, or 1) axes of x:
+    ([high_0 ..] finest first, low, the highs' device pointers as the multi-level launchers take them)."""
+    lead, size = tuple(x.shape[:-axes]), tuple(x.shape[-axes:])
+    band = (3,) if axes == 2 else ()
+    yh = []
+    for _ in range(nlev):
+        size = tuple(coeff_len(n, L, mode) for n in size)
+        yh.append(torch.empty(lead + band + size, dtype=x.dtype, device=x.device))
+    yl = torch.empty(lead + size, dtype=x.dtype, device=x.device)
+    return yh, yl, (ctypes.c_void_p * nlev)(*[t.data_ptr() for t in yh])
+
+
 def _plane_strides(t):
     """(plane stride, row stride) in elements of a (N,C,H,W) tensor whose (n,c) planes are uniformly spaced and whose
     columns have unit stride - or None when it has no such description (the caller then makes it dense).  The stride of a
@@ -151,10 +186,7 @@ def sfb2d(ll, highs, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, out_hw=None):
         _same_device(ll, highs)
     gwl, gwh, ghl, ghh = (_taps(g, ll) for g in (g_w_lo, g_w_hi, g_h_lo, g_h_hi))
     Lw, Lh = gwl.numel(), ghl.numel()
-    OH = 2 * Kh if mode == 2 else 2 * Kh - Lh + 2
-    OW = 2 * Kw if mode == 2 else 2 * Kw - Lw + 2
-    if out_hw is not None:
-        OH, OW = min(OH, out_hw[0]), min(OW, out_hw[1])
+    OH, OW = _synth_hw(Kh, Kw, Lh, Lw, mode, out_hw)
     y = torch.empty((N, C, OH, OW), dtype=ll.dtype, device=ll.device)
     rc = _call('wl_dwt2d_synthesis', ll, ll.data_ptr(), ll_ps, ll_rs,
                                        None if highs is None else highs.data_ptr(), y.data_ptr(),
@@ -261,9 +293,24 @@ def _new_tap_scratch(device):
     return torch.empty(TAP_SCRATCH_FLOATS, dtype=torch.float32, device=device)
 
 
-def _plain_taps(bufs, ref):
-    """The entry of an unhinted launch: converted taps, no scratch, a state word nobody reads."""
-    return [tuple(_taps(b, ref) for b in bufs), None, ctypes.c_int(0)]
+def _launch_taps(bufs, ref, L, syn, hinted):
+    """The taps of one launch of an *_ex entry point: (taps, scratch pointer or None, state word).  Hinted: the entry of
+    _hinted_taps (a hint is only ever set together with the tap cache - qmf_hint -, which keeps the scratch alive past this
+    call); unhinted: converted taps, no scratch, a state word nobody reads."""
+    if not hinted:
+        return tuple(_taps(b, ref) for b in bufs), None, ctypes.c_int(0)
+    taps, scratch, tstate = _hinted_taps(bufs, ref, L, syn)
+    return taps, None if scratch is None else scratch.data_ptr(), tstate
+
+
+def _fused_hint_bits(same, qmf):
+    """Bits 2 and 3 of the `strips` argument of the fused (multi-level) launchers."""
+    return (4 if same else 0) | (8 if qmf else 0)
+
+
+def _strip_policy_bits(force, qmf):
+    """The `policy` argument of the one-level strip launchers."""
+    return (1 if force else 0) | (2 if qmf else 0)
 
 
 def current_hints():
@@ -324,6 +371,18 @@ def _remember_decline(key):
     _FUSED_DECLINED.add(key)
 
 
+def _declined(key, name, ref, *args, memo=True):
+    """One C-ABI call of a launcher that may decline: True when it did (WL_ERR_UNSUPPORTED; remembered under `key` unless
+    `memo` is false), False when it ran; any other failure raises."""
+    rc = _call(name, ref, *args)
+    if rc == _lib.WL_ERR_UNSUPPORTED:
+        if memo:
+            _remember_decline(key)
+        return True
+    _lib.check(rc, name)
+    return False
+
+
 def set_option(name, value):
     """wl_set_option of the C ABI ('generic_only', 'no_stream', 'scat_stream'); forgets the memoised declines, which may
     depend on the options."""
@@ -348,7 +407,6 @@ def afb2d_fused(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, nlev, strips=None, whol
     some planes in two to fill whole rounds), 1 = force, whole planes only, 2 = force, every plane cut in two.  x may be a row-padded
     view (rows on 16-byte addresses; the width itself need not be a whole number of 16-byte pieces then).  `whole`: this launch is the
     entire transform (a one-level launch on rows of 2-3 KiB is taken only then: inside a longer pyramid the strip kernel is ahead)."""
-    import ctypes
     _check_tensor(x, 'x')
     if strips is None:
         strips = FUSED_STRIPS
@@ -359,8 +417,7 @@ def afb2d_fused(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, nlev, strips=None, whol
     # of its lowpass bank - HINTS: the kernel variants that rely on them verify them on the device, the two-bank variant stands by
     # behind them, so a stale hint costs an empty launch, never a wrong coefficient.  With both, 10-20 taps run the LATTICE variant
     # (csrc/wl_lattice.h): the only fused form of 14, 16 and 20 taps.
-    same = bool(getattr(_HINTS, 'same', False))
-    qmf = bool(getattr(_HINTS, 'qmf', False))
+    qmf, same = current_hints()
     # (periodization with 12 taps: its odd-cell instantiations are the lattice variant and the two-bank direct form, which spills)
     lattice = (same and qmf and ROWS_LATTICE and L in (8, 10, 12, 14, 16, 18, 20) and L >= ROWS_LATTICE_MIN
                and (L > 12 or x.numel() >= LATTICE_MIN_ELEMS or (mode == 2 and L == 12)))
@@ -395,23 +452,12 @@ def afb2d_fused(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, nlev, strips=None, whol
     key = ('afb', x.device, x.dtype, N * C, H, W, x_ps, x_rs, L, mode, nlev, strips, lattice)
     if key in _FUSED_DECLINED:
         return None
-    ent = _hinted_taps((h_w_lo, h_w_hi, h_h_lo, h_h_hi), x, L, False) if lattice else _plain_taps((h_w_lo, h_w_hi, h_h_lo, h_h_hi), x)
-    (hwl, hwh, hhl, hhh), scratch, tstate = ent
-    same = (4 if same else 0) | (8 if qmf else 0)
-    yh = []
-    h, w = H, W
-    for _ in range(nlev):
-        h, w = coeff_len(h, L, mode), coeff_len(w, L, mode)
-        yh.append(torch.empty((N, C, 3, h, w), dtype=x.dtype, device=x.device))
-    yl = torch.empty((N, C, h, w), dtype=x.dtype, device=x.device)
-    ptrs = (ctypes.c_void_p * nlev)(*[t.data_ptr() for t in yh])
-    rc = _call('wl_dwt2d_analysis_fused_ex', x, x.data_ptr(), x_ps, x_rs, yl.data_ptr(), ptrs, _DTYPES[x.dtype], N * C, H, W, nlev,
-               hwl.data_ptr(), hwh.data_ptr(), hhl.data_ptr(), hhh.data_ptr(), L, mode, strips | same,
-               None if scratch is None else scratch.data_ptr(), ctypes.byref(tstate), _stream(x))
-    if rc == -3:
-        _remember_decline(key)
+    (hwl, hwh, hhl, hhh), scratch, tstate = _launch_taps((h_w_lo, h_w_hi, h_h_lo, h_h_hi), x, L, False, lattice)
+    yh, yl, ptrs = _new_pyramid(x, nlev, L, mode, 2)
+    if _declined(key, 'wl_dwt2d_analysis_fused_ex', x, x.data_ptr(), x_ps, x_rs, yl.data_ptr(), ptrs, _DTYPES[x.dtype], N * C, H, W, nlev,
+                 hwl.data_ptr(), hwh.data_ptr(), hhl.data_ptr(), hhh.data_ptr(), L, mode, strips | _fused_hint_bits(same, qmf),
+                 scratch, ctypes.byref(tstate), _stream(x)):
         return None
-    _lib.check(rc, 'wl_dwt2d_analysis_fused_ex')
     return yl, yh
 
 
@@ -421,7 +467,6 @@ SMALL_PLANES = True   # planes of up to ~72 x 72 go to the several-planes-per-wo
 def afb2d_small(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, nlev):
     """`nlev` (1..4) analysis levels of small planes in ONE launch, several planes per workgroup (wl_dwt2d_analysis_small):
     x (N,C,H,W) -> (yl, [yh_0..]) like afb2d_fused, or None when the kernel does not cover the configuration."""
-    import ctypes
     _check_tensor(x, 'x')
     N, C, H, W = x.shape
     L = h_w_lo.numel()
@@ -433,19 +478,10 @@ def afb2d_small(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, nlev):
         return None
     x = x.contiguous()
     hwl, hwh, hhl, hhh = (_taps(h, x) for h in (h_w_lo, h_w_hi, h_h_lo, h_h_hi))
-    yh = []
-    h, w = H, W
-    for _ in range(nlev):
-        h, w = coeff_len(h, L, mode), coeff_len(w, L, mode)
-        yh.append(torch.empty((N, C, 3, h, w), dtype=x.dtype, device=x.device))
-    yl = torch.empty((N, C, h, w), dtype=x.dtype, device=x.device)
-    ptrs = (ctypes.c_void_p * nlev)(*[t.data_ptr() for t in yh])
-    rc = _call('wl_dwt2d_analysis_small', x, x.data_ptr(), yl.data_ptr(), ptrs, _DTYPES[x.dtype], N * C, H, W, nlev,
-               hwl.data_ptr(), hwh.data_ptr(), hhl.data_ptr(), hhh.data_ptr(), L, mode, _stream(x))
-    if rc == -3:
-        _remember_decline(key)
+    yh, yl, ptrs = _new_pyramid(x, nlev, L, mode, 2)
+    if _declined(key, 'wl_dwt2d_analysis_small', x, x.data_ptr(), yl.data_ptr(), ptrs, _DTYPES[x.dtype], N * C, H, W, nlev,
+                 hwl.data_ptr(), hwh.data_ptr(), hhl.data_ptr(), hhh.data_ptr(), L, mode, _stream(x)):
         return None
-    _lib.check(rc, 'wl_dwt2d_analysis_small')
     return yl, yh
 
 
@@ -453,7 +489,6 @@ def sfb2d_small(yl, yh, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode):
     """All len(yh) (1..4) synthesis levels of small planes in ONE launch, several planes per workgroup
     (wl_dwt2d_synthesis_small): yl (N,C,h,w), yh = [finest .. coarsest] of (N,C,3,Kh_j,Kw_j) -> x (N,C,OH,OW) like sfb2d_fused,
     or None when the kernel does not cover the configuration."""
-    import ctypes
     _check_tensor(yl, 'yl')
     nlev = len(yh)
     N, C, h, w = yl.shape
@@ -462,8 +497,7 @@ def sfb2d_small(yl, yh, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode):
             or g_h_lo.numel() != L or L % 2 or L > 20 or yl.numel() == 0 or mode not in _MODE_TO_EXT
             or any(t is None or t.dim() != 5 or t.dtype != yl.dtype or t.shape[:3] != (N, C, 3) or t.numel() == 0 for t in yh)):
         return None
-    kh0, kw0 = yh[0].shape[3], yh[0].shape[4]
-    OH, OW = (2 * kh0, 2 * kw0) if mode == 2 else (2 * kh0 - L + 2, 2 * kw0 - L + 2)
+    OH, OW = _synth_hw(yh[0].shape[3], yh[0].shape[4], L, L, mode)
     if OH < 1 or OW < 1 or OH * OW > 5184:
         return None
     key = ('sfbsm', yl.device, yl.dtype, N * C, h, w, tuple(tuple(t.shape[3:]) for t in yh), L, mode)
@@ -478,12 +512,9 @@ def sfb2d_small(yl, yh, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode):
     ptrs = (ctypes.c_void_p * nlev)(*[t.data_ptr() for t in yh])
     khs = (ctypes.c_int * nlev)(*[t.shape[3] for t in yh])
     kws = (ctypes.c_int * nlev)(*[t.shape[4] for t in yh])
-    rc = _call('wl_dwt2d_synthesis_small', yl, yl.data_ptr(), h, w, ptrs, khs, kws, y.data_ptr(), _DTYPES[yl.dtype], N * C, nlev,
-               gwl.data_ptr(), gwh.data_ptr(), ghl.data_ptr(), ghh.data_ptr(), L, mode, _stream(yl))
-    if rc == -3:
-        _remember_decline(key)
+    if _declined(key, 'wl_dwt2d_synthesis_small', yl, yl.data_ptr(), h, w, ptrs, khs, kws, y.data_ptr(), _DTYPES[yl.dtype], N * C, nlev,
+                 gwl.data_ptr(), gwh.data_ptr(), ghl.data_ptr(), ghh.data_ptr(), L, mode, _stream(yl)):
         return None
-    _lib.check(rc, 'wl_dwt2d_synthesis_small')
     return y
 
 
@@ -491,7 +522,6 @@ def sfb2d_fused(yl, yh, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, strips=None):
     """All len(yh) (1..3) synthesis levels in ONE launch of the streaming kernel: yl (N,C,h,w) [may be a strided crop],
     yh = [finest .. coarsest] of (N,C,3,Kh_j,Kw_j) -> x (N,C,OH,OW).  The intermediate low-passes never leave the
     chip.  Returns None when the kernel does not cover the configuration (caller goes level by level)."""
-    import ctypes
     _check_tensor(yl, 'yl')
     if strips is None:
         strips = FUSED_STRIPS
@@ -500,8 +530,7 @@ def sfb2d_fused(yl, yh, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, strips=None):
     L = g_w_lo.numel()
     es = yl.element_size()
     # (hints as in afb2d_fused: with "same banks" and "quadrature-mirror highpass" 10-20 taps run the lattice variant of the kernel)
-    same = bool(getattr(_HINTS, 'same', False))
-    qmf = bool(getattr(_HINTS, 'qmf', False))
+    qmf, same = current_hints()
     lattice = (same and qmf and ROWS_LATTICE and L in (8, 10, 12, 14, 16, 18, 20) and L >= IROWS_LATTICE_MIN
                and (L > 12 or (nlev >= 1 and yh[0] is not None and yh[0].dim() == 5
                                and 4 * yh[0].shape[3] * yh[0].shape[4] * N * C >= (LATTICE_MIN_ELEMS if nlev == 1 else min(LATTICE_MIN_ELEMS, LATTICE_MIN_ELEMS_ML)))))
@@ -533,7 +562,7 @@ def sfb2d_fused(yl, yh, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, strips=None):
         kh, kw = t.shape[3], t.shape[4]
         if not (kh <= sh <= kh + 1 and kw <= sw <= kw + 1) or kh < L // 2 or kw < L // 2 or (per and (sh, sw) != (kh, kw)):
             return None
-        sh, sw = (2 * kh, 2 * kw) if per else (2 * kh - L + 2, 2 * kw - L + 2)
+        sh, sw = _synth_hw(kh, kw, L, L, mode)
     # the kernel copies the coarsest low-pass like a band plane: dense rows of the coarsest high-pass width
     kh, kw = yh[-1].shape[3], yh[-1].shape[4]
     if (h, w) != (kh, kw):
@@ -549,20 +578,15 @@ def sfb2d_fused(yl, yh, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, strips=None):
     key = ('sfb', yl.device, yl.dtype, N * C, kh, kw, tuple(tuple(t.shape[3:]) for t in yh), L, mode, strips, lattice)
     if key in _FUSED_DECLINED or yl.data_ptr() % 4 or any(t.data_ptr() % 4 for t in yh):
         return None
-    ent = _hinted_taps((g_w_lo, g_w_hi, g_h_lo, g_h_hi), yl, L, True) if lattice else _plain_taps((g_w_lo, g_w_hi, g_h_lo, g_h_hi), yl)
-    (gwl, gwh, ghl, ghh), scratch, tstate = ent
-    hint_bits = (4 if same else 0) | (8 if qmf else 0)
+    (gwl, gwh, ghl, ghh), scratch, tstate = _launch_taps((g_w_lo, g_w_hi, g_h_lo, g_h_hi), yl, L, True, lattice)
     y = torch.empty((N, C, sh, sw), dtype=yl.dtype, device=yl.device)
     ptrs = (ctypes.c_void_p * nlev)(*[t.data_ptr() for t in yh])
     khs = (ctypes.c_int * nlev)(*[t.shape[3] for t in yh])
     kws = (ctypes.c_int * nlev)(*[t.shape[4] for t in yh])
-    rc = _call('wl_dwt2d_synthesis_fused_ex', yl, yl.data_ptr(), yl_ps, yl_rs, kh, kw, ptrs, khs, kws,
-               y.data_ptr(), _DTYPES[yl.dtype], N * C, nlev, gwl.data_ptr(), gwh.data_ptr(), ghl.data_ptr(),
-               ghh.data_ptr(), L, mode, strips | hint_bits, None if scratch is None else scratch.data_ptr(), ctypes.byref(tstate), _stream(yl))
-    if rc == -3:
-        _remember_decline(key)
+    if _declined(key, 'wl_dwt2d_synthesis_fused_ex', yl, yl.data_ptr(), yl_ps, yl_rs, kh, kw, ptrs, khs, kws,
+                 y.data_ptr(), _DTYPES[yl.dtype], N * C, nlev, gwl.data_ptr(), gwh.data_ptr(), ghl.data_ptr(),
+                 ghh.data_ptr(), L, mode, strips | _fused_hint_bits(same, qmf), scratch, ctypes.byref(tstate), _stream(yl)):
         return None
-    _lib.check(rc, 'wl_dwt2d_synthesis_fused_ex')
     return y
 
 
@@ -607,12 +631,11 @@ def afb2d_stream(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, force=False, pad_ll=Fa
     if not force and W < STRIP_MINW:
         return None                      # the engine's policy: narrower rows stay on the tile kernels (the launcher decides the rest)
     x, x_ps, x_rs = _planes(x)
-    qmf = bool(getattr(_HINTS, 'qmf', False))
+    qmf = current_hints()[0]
     key = ('afbs', x.device, x.dtype, N * C, H, W, x_ps, x_rs, L, mode, bool(force), qmf, bool(pad_ll))
     if key in _FUSED_DECLINED:
         return None
-    ent = _hinted_taps((h_w_lo, h_w_hi, h_h_lo, h_h_hi), x, L, False) if qmf else _plain_taps((h_w_lo, h_w_hi, h_h_lo, h_h_hi), x)
-    (hwl, hwh, hhl, hhh), scratch, tstate = ent
+    (hwl, hwh, hhl, hhh), scratch, tstate = _launch_taps((h_w_lo, h_w_hi, h_h_lo, h_h_hi), x, L, False, qmf)
     Kh, Kw = coeff_len(H, L, mode), coeff_len(W, L, mode)
     q = 16 // es
     Kp = (Kw + q - 1) // q * q if pad_ll else Kw
@@ -620,13 +643,10 @@ def afb2d_stream(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, force=False, pad_ll=Fa
     if Kp != Kw:
         ll = ll[..., :Kw]
     highs = torch.empty((N, C, 3, Kh, Kw), dtype=x.dtype, device=x.device)
-    rc = _call('wl_dwt2d_analysis_stream_ex', x, x.data_ptr(), x_ps, x_rs, ll.data_ptr(), Kh * Kp, Kp, highs.data_ptr(),
-               _DTYPES[x.dtype], N * C, H, W, hwl.data_ptr(), hwh.data_ptr(), hhl.data_ptr(), hhh.data_ptr(), L, mode,
-               (1 if force else 0) | (2 if qmf else 0), None if scratch is None else scratch.data_ptr(), ctypes.byref(tstate), _stream(x))
-    if rc == -3:
-        _remember_decline(key)
+    if _declined(key, 'wl_dwt2d_analysis_stream_ex', x, x.data_ptr(), x_ps, x_rs, ll.data_ptr(), Kh * Kp, Kp, highs.data_ptr(),
+                 _DTYPES[x.dtype], N * C, H, W, hwl.data_ptr(), hwh.data_ptr(), hhl.data_ptr(), hhh.data_ptr(), L, mode,
+                 _strip_policy_bits(force, qmf), scratch, ctypes.byref(tstate), _stream(x)):
         return None
-    _lib.check(rc, 'wl_dwt2d_analysis_stream_ex')
     return ll, highs
 
 
@@ -644,29 +664,22 @@ def sfb2d_stream(ll, highs, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, out_hw=None, f
             or tuple(highs.shape) != (N, C, 3, Kh, Kw) or highs.dtype != ll.dtype
             or (mode == 2 and (2 * Kh < L - 2 or 2 * Kw < L - 2))):
         return None
-    OH = 2 * Kh if mode == 2 else 2 * Kh - L + 2
-    OW = 2 * Kw if mode == 2 else 2 * Kw - L + 2
-    if out_hw is not None:
-        OH, OW = min(OH, out_hw[0]), min(OW, out_hw[1])
+    OH, OW = _synth_hw(Kh, Kw, L, L, mode, out_hw)
     if not force and (OW < STRIP_MINW or OW % 4):
         return None                      # the engine's policy: narrow rows / unaligned 4-column groups stay on the other kernels
     ll, ll_ps, ll_rs = _planes(ll)
     highs = highs.contiguous()
     _same_device(ll, highs)
-    qmf = bool(getattr(_HINTS, 'qmf', False))
+    qmf = current_hints()[0]
     key = ('sfbs', ll.device, ll.dtype, N * C, Kh, Kw, ll_ps, ll_rs, OH, OW, L, mode, bool(force), qmf)
     if key in _FUSED_DECLINED:
         return None
-    ent = _hinted_taps((g_w_lo, g_w_hi, g_h_lo, g_h_hi), ll, L, True) if qmf else _plain_taps((g_w_lo, g_w_hi, g_h_lo, g_h_hi), ll)
-    (gwl, gwh, ghl, ghh), scratch, tstate = ent
+    (gwl, gwh, ghl, ghh), scratch, tstate = _launch_taps((g_w_lo, g_w_hi, g_h_lo, g_h_hi), ll, L, True, qmf)
     y = torch.empty((N, C, OH, OW), dtype=ll.dtype, device=ll.device)
-    rc = _call('wl_dwt2d_synthesis_stream_ex', ll, ll.data_ptr(), ll_ps, ll_rs, highs.data_ptr(), y.data_ptr(), _DTYPES[ll.dtype],
-               N * C, Kh, Kw, OH, OW, gwl.data_ptr(), gwh.data_ptr(), ghl.data_ptr(), ghh.data_ptr(), L, mode,
-               (1 if force else 0) | (2 if qmf else 0), None if scratch is None else scratch.data_ptr(), ctypes.byref(tstate), _stream(ll))
-    if rc == -3:
-        _remember_decline(key)
+    if _declined(key, 'wl_dwt2d_synthesis_stream_ex', ll, ll.data_ptr(), ll_ps, ll_rs, highs.data_ptr(), y.data_ptr(), _DTYPES[ll.dtype],
+                 N * C, Kh, Kw, OH, OW, gwl.data_ptr(), gwh.data_ptr(), ghl.data_ptr(), ghh.data_ptr(), L, mode,
+                 _strip_policy_bits(force, qmf), scratch, ctypes.byref(tstate), _stream(ll)):
         return None
-    _lib.check(rc, 'wl_dwt2d_synthesis_stream_ex')
     return y
 
 
@@ -724,10 +737,7 @@ def sfb2d_nonsep(coeffs, filts, mode, out_hw=None):
     coeffs = coeffs.contiguous()
     Ly, Lx = filts.shape[2], filts.shape[3]
     g = _taps(filts, coeffs)
-    OH = 2 * Kh if mode == 2 else 2 * Kh - Ly + 2
-    OW = 2 * Kw if mode == 2 else 2 * Kw - Lx + 2
-    if out_hw is not None:
-        OH, OW = min(OH, out_hw[0]), min(OW, out_hw[1])
+    OH, OW = _synth_hw(Kh, Kw, Ly, Lx, mode, out_hw)
     y = torch.empty((N, C, OH, OW), dtype=coeffs.dtype, device=coeffs.device)
     if coeffs.numel():
         rc = _call('wl_dwt2d_synthesis_nonsep', coeffs, coeffs.data_ptr(), y.data_ptr(), _DTYPES[coeffs.dtype], N * C,
@@ -787,12 +797,7 @@ def corr1d(x, dim, h0, h1, K, start, step, tap_step=1, ext=EXT_SYM, taps=None, o
     x = x.contiguous()
     dim = dim % x.dim()
     n = x.shape[dim]
-    outer = 1
-    for v in x.shape[:dim]:
-        outer *= v
-    inner = 1
-    for v in x.shape[dim + 1:]:
-        inner *= v
+    outer, inner = _outer_inner(x.shape, dim)
     t0 = _taps(h0, x)
     t1 = None if h1 is None else _taps(h1, x)
     off, ts, nt = taps if taps is not None else (0, 1, t0.numel())
@@ -833,7 +838,6 @@ def afb1d_fused(x, h0, h1, mode, J):
     """J (1..4) analysis levels along the LAST axis in ONE launch (wl_dwt1d_analysis_fused: every input sample read once, the
     intermediate lowpass signals stay in LDS): x (..., n) -> (lo, [hi_1 .. hi_J]) finest first, or None when the kernel does
     not cover the configuration (callers go level by level on afb1d)."""
-    import ctypes
     _check_tensor(x, 'x')
     L = h0.numel()
     n = x.shape[-1]
@@ -846,19 +850,10 @@ def afb1d_fused(x, h0, h1, mode, J):
     if key in _FUSED_DECLINED:
         return None
     t0, t1 = _taps(h0, x), _taps(h1, x)
-    lens, m = [], n
-    for _ in range(J):
-        m = coeff_len(m, L, mode)
-        lens.append(m)
-    his = [torch.empty(x.shape[:-1] + (m,), dtype=x.dtype, device=x.device) for m in lens]
-    lo = torch.empty(x.shape[:-1] + (lens[-1],), dtype=x.dtype, device=x.device)
-    ptrs = (ctypes.c_void_p * J)(*[t.data_ptr() for t in his])
-    rc = _call('wl_dwt1d_analysis_fused', x, x.data_ptr(), lo.data_ptr(), ptrs, _DTYPES[x.dtype], rows, n, J, t0.data_ptr(),
-               t1.data_ptr(), L, mode, _stream(x))
-    if rc == -3:
-        _remember_decline(key)
+    his, lo, ptrs = _new_pyramid(x, J, L, mode, 1)
+    if _declined(key, 'wl_dwt1d_analysis_fused', x, x.data_ptr(), lo.data_ptr(), ptrs, _DTYPES[x.dtype], rows, n, J, t0.data_ptr(),
+                 t1.data_ptr(), L, mode, _stream(x)):
         return None
-    _lib.check(rc, 'wl_dwt1d_analysis_fused')
     return lo, his
 
 
@@ -881,12 +876,9 @@ def swt2d_level(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, dilation, ext):
         return None
     taps = [_taps(h, x) for h in (h_w_lo, h_w_hi, h_h_lo, h_h_hi)]
     y = torch.empty((N, 4 * C, H, W), dtype=x.dtype, device=x.device)
-    rc = _call('wl_swt2d_level', x, x.data_ptr(), st[0], y.data_ptr(), _DTYPES[x.dtype], N * C, H, W,
-               taps[0].data_ptr(), taps[1].data_ptr(), taps[2].data_ptr(), taps[3].data_ptr(), Lw, Lh, dilation, ext, _stream(x))
-    if rc == -3:
-        _remember_decline(key)
+    if _declined(key, 'wl_swt2d_level', x, x.data_ptr(), st[0], y.data_ptr(), _DTYPES[x.dtype], N * C, H, W,
+                 taps[0].data_ptr(), taps[1].data_ptr(), taps[2].data_ptr(), taps[3].data_ptr(), Lw, Lh, dilation, ext, _stream(x)):
         return None
-    _lib.check(rc, 'wl_swt2d_level')
     return y
 
 
@@ -928,13 +920,10 @@ def iswt2d_level(y, h_w_lo, h_w_hi, h_h_lo, h_h_hi, dilation, ext, scale=1.0, ll
         return None
     taps = [_taps(h, ref) for h in (h_w_lo, h_w_hi, h_h_lo, h_h_hi)]
     x = torch.empty((N, C, H, W), dtype=ref.dtype, device=ref.device)
-    rc = _call('wl_iswt2d_level', ref, None if y is None else y.data_ptr(), 4 * H * W, None if ll is None else ll.data_ptr(), ll_ps,
-               ll_mode, x.data_ptr(), _DTYPES[ref.dtype], N * C, H, W, taps[0].data_ptr(), taps[1].data_ptr(), taps[2].data_ptr(),
-               taps[3].data_ptr(), Lw, Lh, dilation, ext, float(scale), _stream(ref))
-    if rc == -3:
-        _remember_decline(key)
+    if _declined(key, 'wl_iswt2d_level', ref, None if y is None else y.data_ptr(), 4 * H * W, None if ll is None else ll.data_ptr(), ll_ps,
+                 ll_mode, x.data_ptr(), _DTYPES[ref.dtype], N * C, H, W, taps[0].data_ptr(), taps[1].data_ptr(), taps[2].data_ptr(),
+                 taps[3].data_ptr(), Lw, Lh, dilation, ext, float(scale), _stream(ref)):
         return None
-    _lib.check(rc, 'wl_iswt2d_level')
     return x
 
 
@@ -991,12 +980,7 @@ def corr1d_adj(y0, y1, dim, h0, h1, n, start, tap_step=1, ext=EXT_SYM, scale=1.0
     y0, os0 = _with_outer_stride(y0, dim)
     y1, os1 = _with_outer_stride(y1, dim)
     K = y0.shape[dim]
-    outer = 1
-    for v in y0.shape[:dim]:
-        outer *= v
-    inner = 1
-    for v in y0.shape[dim + 1:]:
-        inner *= v
+    outer, inner = _outer_inner(y0.shape, dim)
     t0 = _taps(h0, y0)
     t1 = None if h1 is None else _taps(h1, y0)
     shape = list(y0.shape)
@@ -1014,7 +998,6 @@ def sfb1d_fused(lo, his, g0, g1, mode, out_len=None):
     """All len(his) (1..4) synthesis levels along the LAST axis in ONE launch (wl_dwt1d_synthesis_fused): lo (..., n_lo), his =
     [finest .. coarsest] (None = zeros) -> y (..., out_len) (default: the full reconstruction 2 n_hi[0] - L + 2), or None when
     the kernel does not cover the configuration (callers go level by level on sfb1d)."""
-    import ctypes
     _check_tensor(lo, 'lo')
     J, L = len(his), g0.numel()
     if (lo.dtype == torch.float64 or J < 1 or J > 4 or L % 2 or L > 20 or g1.numel() != L or lo.numel() == 0 or mode == 2
@@ -1028,7 +1011,7 @@ def sfb1d_fused(lo, his, g0, g1, mode, out_len=None):
         if h.dtype != lo.dtype or h.shape[:-1] != lo.shape[:-1]:
             return None
         lens.append(h.shape[-1])
-    full = 2 * lens[0] - L + 2
+    full = synth_len(lens[0], L, mode)
     if out_len is None:
         out_len = full
     if out_len < 1 or out_len > full:
@@ -1045,12 +1028,9 @@ def sfb1d_fused(lo, his, g0, g1, mode, out_len=None):
     y = torch.empty(lo.shape[:-1] + (out_len,), dtype=lo.dtype, device=lo.device)
     ptrs = (ctypes.c_void_p * J)(*[h.data_ptr() for h in his])
     ns = (ctypes.c_int * J)(*lens)
-    rc = _call('wl_dwt1d_synthesis_fused', lo, lo.data_ptr(), lo.shape[-1], ptrs, ns, y.data_ptr(), out_len, _DTYPES[lo.dtype], rows, J,
-               t0.data_ptr(), t1.data_ptr(), L, mode, _stream(lo))
-    if rc == -3:
-        _remember_decline(key)
+    if _declined(key, 'wl_dwt1d_synthesis_fused', lo, lo.data_ptr(), lo.shape[-1], ptrs, ns, y.data_ptr(), out_len, _DTYPES[lo.dtype], rows, J,
+                 t0.data_ptr(), t1.data_ptr(), L, mode, _stream(lo)):
         return None
-    _lib.check(rc, 'wl_dwt1d_synthesis_fused')
     return y
 
 
@@ -1065,15 +1045,8 @@ def sfb1d(lo, hi, g0, g1, mode, dim, out_len=None):
         if hi.shape != lo.shape:
             raise ValueError('lo %s and hi %s differ in shape' % (tuple(lo.shape), tuple(hi.shape)))
         _same_device(lo, hi)
-    ny = 2 * K if mode == 2 else 2 * K - L + 2
-    if out_len is not None:
-        ny = min(ny, out_len)
-    outer = 1
-    for v in lo.shape[:dim]:
-        outer *= v
-    inner = 1
-    for v in lo.shape[dim + 1:]:
-        inner *= v
+    ny = synth_len(K, L, mode, out_len)
+    outer, inner = _outer_inner(lo.shape, dim)
     shape = list(lo.shape)
     shape[dim] = ny
     y = torch.empty(shape, dtype=lo.dtype, device=lo.device)
@@ -1086,11 +1059,6 @@ def sfb1d(lo, hi, g0, g1, mode, dim, out_len=None):
 
 
 # ---------------------------------------------------------------------------------------------- DTCWT
-def _ll_view(ll, ref_shape):
-    """(ptr, plane_stride, row_stride) of a (N,C,h,w) view whose rows are unit-stride."""
-    return _planes(ll)
-
-
 def dtcwt_fwd1(x, h0, h1, mode, skip_hps=False):
     """Level-1 forward: x (N,C,H,W) -> ll (N,C,He,We), highs (N,C,6,He/2,We/2,2) or None."""
     _check_tensor(x, 'x')
@@ -1128,13 +1096,10 @@ def dtcwt_fwd1_rot(x, h0, h1, h2, symmetric, scat=False, magbias=0.0):
         ll = torch.empty((N, C, H, W), dtype=x.dtype, device=x.device)
         re = torch.empty((N, 6, C, h2_, w2_), dtype=x.dtype, device=x.device)
         im = torch.empty_like(re)
-    rc = _call('wl_dtcwt_fwd_level1_rot', x, x.data_ptr(), None if ll is None else ll.data_ptr(), re.data_ptr(),
-               None if im is None else im.data_ptr(), _DTYPES[x.dtype], N, C, H, W, t0.data_ptr(), t0.numel(), t1.data_ptr(),
-               t1.numel(), t2.data_ptr(), t2.numel(), 1 if symmetric else 0, 1 if scat else 0, float(magbias), _stream(x))
-    if rc == -3:
-        _remember_decline(key)
+    if _declined(key, 'wl_dtcwt_fwd_level1_rot', x, x.data_ptr(), None if ll is None else ll.data_ptr(), re.data_ptr(),
+                 None if im is None else im.data_ptr(), _DTYPES[x.dtype], N, C, H, W, t0.data_ptr(), t0.numel(), t1.data_ptr(),
+                 t1.numel(), t2.data_ptr(), t2.numel(), 1 if symmetric else 0, 1 if scat else 0, float(magbias), _stream(x)):
         return None
-    _lib.check(rc, 'wl_dtcwt_fwd_level1_rot')
     return re if scat else (ll, re, im)
 
 
@@ -1157,15 +1122,11 @@ def dtcwt_fwd12(x, h0o, h1o, h0a, h0b, h1a, h1b, mode, force=False):
     highs1 = torch.empty((N, C, 6, H // 2, W // 2, 2), dtype=x.dtype, device=x.device)
     ll2 = torch.empty((N, C, H // 2, W // 2), dtype=x.dtype, device=x.device)
     highs2 = torch.empty((N, C, 6, H // 4, W // 4, 2), dtype=x.dtype, device=x.device)
-    rc = _call('wl_dtcwt_fwd_level12', x, x.data_ptr(), highs1.data_ptr(), ll2.data_ptr(), highs2.data_ptr(),
-               _DTYPES[x.dtype], N * C, H, W, t0.data_ptr(), t0.numel(), t1.data_ptr(), t1.numel(), ta.data_ptr(),
-               tb.data_ptr(), tc.data_ptr(), td.data_ptr(), ta.numel(), mode, 1 if force else 0, _stream(x))
-    if rc == -3:   # WL_ERR_UNSUPPORTED
-        # (a decline is remembered - unless it is the streaming kernels being switched off for a test / an A/B run)
-        if not force:
-            _remember_decline(key)
+    # (a decline is remembered - unless it is the streaming kernels being switched off for a test / an A/B run)
+    if _declined(key, 'wl_dtcwt_fwd_level12', x, x.data_ptr(), highs1.data_ptr(), ll2.data_ptr(), highs2.data_ptr(),
+                 _DTYPES[x.dtype], N * C, H, W, t0.data_ptr(), t0.numel(), t1.data_ptr(), t1.numel(), ta.data_ptr(),
+                 tb.data_ptr(), tc.data_ptr(), td.data_ptr(), ta.numel(), mode, 1 if force else 0, _stream(x), memo=not force):
         return None
-    _lib.check(rc, 'wl_dtcwt_fwd_level12')
     return highs1, ll2, highs2
 
 
@@ -1200,7 +1161,7 @@ def dtcwt_inv1(ll, highs, g0, g1, mode):
         if tuple(ll.shape) != (N, C, H, W):
             raise ValueError('lowpass %s does not match the highpass size %s' % (tuple(ll.shape), (N, C, H, W)))
         _same_device(ll, highs)
-        ll, ps, rs = _ll_view(ll, (N, C))
+        ll, ps, rs = _planes(ll)
     t0, t1 = _taps(g0, ref), _taps(g1, ref)
     y = torch.empty((N, C, H, W), dtype=ref.dtype, device=ref.device)
     rc = _call('wl_dtcwt_inv_level1', ref, None if ll is None else ll.data_ptr(), ps, rs,
@@ -1226,7 +1187,7 @@ def dtcwt_inv2(ll, highs, g0a, g0b, g1a, g1b):
         if tuple(ll.shape) != (N, C, h, w):
             raise ValueError('lowpass %s does not match the highpass size %s' % (tuple(ll.shape), (N, C, h, w)))
         _same_device(ll, highs)
-        ll, ps, rs = _ll_view(ll, (N, C))
+        ll, ps, rs = _planes(ll)
     ta, tb, tc, td = (_taps(g, ref) for g in (g0a, g0b, g1a, g1b))
     y = torch.empty((N, C, 2 * h, 2 * w), dtype=ref.dtype, device=ref.device)
     rc = _call('wl_dtcwt_inv_level2', ref, None if ll is None else ll.data_ptr(), ps, rs,
@@ -1259,14 +1220,10 @@ def dtcwt_inv21(ll2, highs2, highs1, g0o, g1o, g0a, g0b, g1a, g1b, mode, force=F
     t0, t1 = _taps(g0o, ll2), _taps(g1o, ll2)
     ta, tb, tc, td = (_taps(g, ll2) for g in (g0a, g0b, g1a, g1b))
     y = torch.empty((N, C, 2 * h, 2 * w), dtype=ll2.dtype, device=ll2.device)
-    rc = _call('wl_dtcwt_inv_level21', ll2, ll2.data_ptr(), ps, rs, highs2.data_ptr(), highs1.data_ptr(), y.data_ptr(),
-               _DTYPES[ll2.dtype], N * C, 2 * h, 2 * w, t0.data_ptr(), t0.numel(), t1.data_ptr(), t1.numel(), ta.data_ptr(),
-               tb.data_ptr(), tc.data_ptr(), td.data_ptr(), ta.numel(), mode, 1 if force else 0, _stream(ll2))
-    if rc == -3:   # WL_ERR_UNSUPPORTED
-        if not force:
-            _remember_decline(key)
+    if _declined(key, 'wl_dtcwt_inv_level21', ll2, ll2.data_ptr(), ps, rs, highs2.data_ptr(), highs1.data_ptr(), y.data_ptr(),
+                 _DTYPES[ll2.dtype], N * C, 2 * h, 2 * w, t0.data_ptr(), t0.numel(), t1.data_ptr(), t1.numel(), ta.data_ptr(),
+                 tb.data_ptr(), tc.data_ptr(), td.data_ptr(), ta.numel(), mode, 1 if force else 0, _stream(ll2), memo=not force):
         return None
-    _lib.check(rc, 'wl_dtcwt_inv_level21')
     return y
 
 
@@ -1327,13 +1284,8 @@ def scat_fwd2_into(x, z, z_bs, z_ll_off, z_mag_off, h0a, h0b, h1a, h1b, magbias)
     if H % 4 or W % 4 or key in _FUSED_DECLINED:
         return False
     ta, tb, tc, td = (_taps(h, x) for h in (h0a, h0b, h1a, h1b))
-    rc = _call('wl_scat_fwd_level2_into', x, x.data_ptr(), z.data_ptr(), z_bs, z_ll_off, z_mag_off, _DTYPES[x.dtype], N, C, H, W,
-               ta.data_ptr(), tb.data_ptr(), tc.data_ptr(), td.data_ptr(), ta.numel(), float(magbias), _stream(x))
-    if rc == -3:
-        _remember_decline(key)
-        return False
-    _lib.check(rc, 'wl_scat_fwd_level2_into')
-    return True
+    return not _declined(key, 'wl_scat_fwd_level2_into', x, x.data_ptr(), z.data_ptr(), z_bs, z_ll_off, z_mag_off, _DTYPES[x.dtype], N, C, H, W,
+                         ta.data_ptr(), tb.data_ptr(), tc.data_ptr(), td.data_ptr(), ta.numel(), float(magbias), _stream(x))
 
 
 def scat_bwd1(dz, drdx, drdy, h0, h1, mode, combine_colour):
@@ -1352,10 +1304,8 @@ def scat_bwd1(dz, drdx, drdy, h0, h1, mode, combine_colour):
     drdx, drdy = drdx.contiguous(), drdy.contiguous()
     t0, t1 = _taps(h0, dz), _taps(h1, dz)
     dx = torch.empty((N, C, 2 * h2, 2 * w2), dtype=dz.dtype, device=dz.device)
-    rc = _call('wl_scat_bwd_level1', dz, dz.data_ptr(), drdx.data_ptr(), drdy.data_ptr(), dx.data_ptr(), _DTYPES[dz.dtype],
-                                       N, C, 2 * h2, 2 * w2, t0.data_ptr(), t0.numel(), t1.data_ptr(), t1.numel(), mode,
-                                       1 if combine_colour else 0, _stream(dz))
-    if rc == -3:   # WL_ERR_UNSUPPORTED
+    if _declined(None, 'wl_scat_bwd_level1', dz, dz.data_ptr(), drdx.data_ptr(), drdy.data_ptr(), dx.data_ptr(), _DTYPES[dz.dtype],
+                 N, C, 2 * h2, 2 * w2, t0.data_ptr(), t0.numel(), t1.data_ptr(), t1.numel(), mode,
+                 1 if combine_colour else 0, _stream(dz), memo=False):
         return None
-    _lib.check(rc, 'wl_scat_bwd_level1')
     return dx
