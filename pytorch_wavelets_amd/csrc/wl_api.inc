@@ -76,27 +76,16 @@ extern "C" long long wl_last_grid(void) { return wl_last_grid_value(); }
 // for the entry points that live in the other translation units: 1 when the streaming kernels are switched off
 int wl_streaming_off() { return wl_options().no_stream || wl_options().generic_only; }
 
-#define WL_DISPATCH_DTYPE(dtype, CALL)            \
-    switch (dtype) {                              \
-        case WL_F32: { typedef float T; CALL; } break;   \
-        case WL_F16: { typedef wl_half T; CALL; } break; \
-        case WL_BF16: { typedef wl_bf16 T; CALL; } break; \
-        case WL_F64: { typedef double T; CALL; } break;  \
-        default: return WL_ERR_DTYPE;             \
-    }
-
 // ---- DWT analysis ------------------------------------------------------------------------------
-struct WlAfbStrides { int64_t x_ps, ll_ps; int x_rs, ll_rs; };   // plane / row strides of x and ll (elements)
 template <typename T>
-static int wl_afb2d_generic(const WlAfbStrides& st, const void* x, void* ll, void* highs, int64_t planes, int H, int W,
-                            const void* hwl, const void* hwh, int Lw, const void* hhl, const void* hhh,
-                            int Lh, int mode, void* stream) {
+static int wl_afb2d_generic(const WlAfbReq& r) {
     typedef typename WlAcc<T>::type A;
+    const int H = r.H, W = r.W, Lw = r.Lw, Lh = r.Lh, mode = r.mode;
     WlAfb2dArgs<T> a;
-    a.x = (const T*)x; a.ll = (T*)ll; a.highs = (T*)highs;
-    a.h_w_lo = (const A*)hwl; a.h_w_hi = (const A*)hwh; a.h_h_lo = (const A*)hhl; a.h_h_hi = (const A*)hhh;
-    a.NC = planes; a.H = H; a.W = W;
-    a.x_ps = st.x_ps; a.ll_ps = st.ll_ps; a.x_rs = st.x_rs; a.ll_rs = st.ll_rs;
+    a.x = (const T*)r.x; a.ll = (T*)r.ll; a.highs = (T*)r.highs;
+    a.h_w_lo = (const A*)r.taps.w_lo; a.h_w_hi = (const A*)r.taps.w_hi; a.h_h_lo = (const A*)r.taps.h_lo; a.h_h_hi = (const A*)r.taps.h_hi;
+    a.NC = r.planes; a.H = H; a.W = W;
+    a.x_ps = r.x_ps; a.ll_ps = r.ll_ps; a.x_rs = r.x_rs; a.ll_rs = r.ll_rs;
     a.Kh = wl_dwt_coeff_len(H, Lh, mode); a.Kw = wl_dwt_coeff_len(W, Lw, mode);
     a.Lw = Lw; a.Lh = Lh;
     a.basew = wl_afb_base(W, Lw, mode); a.baseh = wl_afb_base(H, Lh, mode);
@@ -113,56 +102,52 @@ static int wl_afb2d_generic(const WlAfbStrides& st, const void* x, void* ll, voi
         if (TW > 16) TW /= 2; else TH /= 2;
     }
     a.tiles_x = wl_cdiv(a.Kw, TW); a.tiles_y = wl_cdiv(a.Kh, TH);
-    return wl_launch<WlAfb2dTile<T> >(a, planes * a.tiles_x * a.tiles_y, wl_afb2d_tile_lds(a), stream);
+    return wl_launch<WlAfb2dTile<T> >(a, r.planes * a.tiles_x * a.tiles_y, wl_afb2d_tile_lds(a), r.stream);
 }
 
 // ---- specialised tile kernel (even tap counts, float / half data) ---------------------------------------
 
 template <typename T, int LT, int TH = 16, int TW = 64, int SH = 0, int V4 = 0>
-static int wl_afb_tile_launch(const WlAfbStrides& st, const void* x, void* ll, void* highs, int64_t planes, int H, int W,
-                              const void* hwl, const void* hwh, const void* hhl, const void* hhh, int mode,
-                              void* stream) {
+static int wl_afb_tile_launch(const WlAfbReq& r) {
     typedef WlAfbTile<T, LT, TH, TW, SH, V4> K;
+    const int64_t planes = r.planes;
+    const int H = r.H, W = r.W, mode = r.mode;
     WlAfbTileArgs<T> a;
-    a.x = (const T*)x; a.ll = (T*)ll; a.highs = (T*)highs;
-    a.h_w_lo = (const float*)hwl; a.h_w_hi = (const float*)hwh;
-    a.h_h_lo = (const float*)hhl; a.h_h_hi = (const float*)hhh;
+    a.x = (const T*)r.x; a.ll = (T*)r.ll; a.highs = (T*)r.highs;
+    a.h_w_lo = (const float*)r.taps.w_lo; a.h_w_hi = (const float*)r.taps.w_hi;
+    a.h_h_lo = (const float*)r.taps.h_lo; a.h_h_hi = (const float*)r.taps.h_hi;
     a.NC = planes; a.H = H; a.W = W;
-    a.x_ps = st.x_ps; a.ll_ps = st.ll_ps; a.x_rs = st.x_rs; a.ll_rs = st.ll_rs;
+    a.x_ps = r.x_ps; a.ll_ps = r.ll_ps; a.x_rs = r.x_rs; a.ll_rs = r.ll_rs;
     a.Kh = wl_dwt_coeff_len(H, LT, mode); a.Kw = wl_dwt_coeff_len(W, LT, mode);
     a.base = wl_afb_base(W, LT, mode);
     a.ext = wl_mode_to_ext(mode);
     a.tiles_x = wl_cdiv(a.Kw, K::TW); a.tiles_y = wl_cdiv(a.Kh, K::TH);
     if (a.tiles_x > 1 && a.Kw - (a.tiles_x - 1) * K::TW <= K::XT) --a.tiles_x;   // the last tile absorbs a short remainder
-    a.vec_ok = (st.x_rs % 2 == 0) && (st.x_ps % 2 == 0) && ((uintptr_t)x % (2 * sizeof(T)) == 0);
+    a.vec_ok = (r.x_rs % 2 == 0) && (r.x_ps % 2 == 0) && ((uintptr_t)r.x % (2 * sizeof(T)) == 0);
     // tiles per workgroup: whole tile rows unless that leaves too few workgroups to fill the chip
     int run = a.tiles_x;
     while (run > 1 && planes * a.tiles_y * wl_cdiv(a.tiles_x, run) < 2048) run = (run + 1) / 2;
     a.run_len = run; a.runs_x = wl_cdiv(a.tiles_x, run);
     a.nblocks = 0;   // XCD-aware remap measured neutral for this kernel: off
-    return wl_launch<K>(a, planes * a.tiles_y * a.runs_x, (size_t)K::kLdsFloats * sizeof(float), stream);
+    return wl_launch<K>(a, planes * a.tiles_y * a.runs_x, (size_t)K::kLdsFloats * sizeof(float), r.stream);
 }
 
 template <typename T>
-static int wl_afb_tile_dispatch(const WlAfbStrides& st, int L, const void* x, void* ll, void* highs, int64_t planes, int H, int W,
-                                const void* hwl, const void* hwh, const void* hhl, const void* hhh, int mode,
-                                void* stream) {
-    if ((int64_t)H * W >= (1LL << 30) || (int64_t)H * st.x_rs >= (1LL << 30) || (int64_t)H * st.ll_rs >= (1LL << 30))
+static int wl_afb_tile_dispatch(const WlAfbReq& r) {   // (Lw == Lh)
+    if ((int64_t)r.H * r.W >= (1LL << 30) || (int64_t)r.H * r.x_rs >= (1LL << 30) || (int64_t)r.H * r.ll_rs >= (1LL << 30))
         return WL_ERR_UNSUPPORTED;
     // float16 rows that allow it are staged with four-element (8-byte) loads: the staged origin 2*kw0 + base - SH is a
     // multiple of four columns when (base - SH) is, and the rows must be 8-byte aligned
-    const bool q4 = sizeof(T) == 2 && (st.x_rs % 4 == 0) && (st.x_ps % 4 == 0) && ((uintptr_t)x % 8 == 0);
+    const bool q4 = sizeof(T) == 2 && (r.x_rs % 4 == 0) && (r.x_ps % 4 == 0) && ((uintptr_t)r.x % 8 == 0);
 #define WL_CASE(LT_)                                                                                                  \
     case LT_: {                                                                                                       \
-        const int base = wl_afb_base(W, LT_, mode);                                                                   \
+        const int base = wl_afb_base(r.W, LT_, r.mode);                                                               \
         const bool v4 = q4 && ((base - (base & 1)) % 4 == 0);                                                         \
         if (base & 1)                                                                                                 \
-            return v4 ? wl_afb_tile_launch<T, LT_, 16, 64, 1, sizeof(T) == 2>(st, x, ll, highs, planes, H, W, hwl, hwh, hhl, hhh, mode, stream) \
-                      : wl_afb_tile_launch<T, LT_, 16, 64, 1, 0>(st, x, ll, highs, planes, H, W, hwl, hwh, hhl, hhh, mode, stream);             \
-        return v4 ? wl_afb_tile_launch<T, LT_, 16, 64, 0, sizeof(T) == 2>(st, x, ll, highs, planes, H, W, hwl, hwh, hhl, hhh, mode, stream)     \
-                  : wl_afb_tile_launch<T, LT_, 16, 64, 0, 0>(st, x, ll, highs, planes, H, W, hwl, hwh, hhl, hhh, mode, stream);                 \
+            return v4 ? wl_afb_tile_launch<T, LT_, 16, 64, 1, sizeof(T) == 2>(r) : wl_afb_tile_launch<T, LT_, 16, 64, 1, 0>(r); \
+        return v4 ? wl_afb_tile_launch<T, LT_, 16, 64, 0, sizeof(T) == 2>(r) : wl_afb_tile_launch<T, LT_, 16, 64, 0, 0>(r);     \
     }
-    switch (L) {
+    switch (r.Lw) {
         // (14 and 18 taps - db7 / sym7, db9 / sym9 - since round 5: without an instantiation every narrow level of theirs fell to the
         // run-time-tap kernel, 0.73 ms for a 128 x 3 x 512 x 512 db7 forward against 0.31 ms)
         WL_CASE(2); WL_CASE(4); WL_CASE(6); WL_CASE(8); WL_CASE(10); WL_CASE(12); WL_CASE(14); WL_CASE(16); WL_CASE(18); WL_CASE(20);
@@ -180,35 +165,31 @@ extern "C" int wl_dwt2d_analysis_strided(const void* x, int64_t x_plane_stride, 
     if (Lw < 1 || Lh < 1 || Lw > WL_MAX_TAPS || Lh > WL_MAX_TAPS) return WL_ERR_TAPS;
     if (x_row_stride < W || ll_row_stride < wl_dwt_coeff_len(W, Lw, mode) || x_plane_stride < 0 || ll_plane_stride < 0)
         return WL_ERR_SHAPE;
-    WlAfbStrides st;
-    st.x_ps = x_plane_stride; st.x_rs = x_row_stride; st.ll_ps = ll_plane_stride; st.ll_rs = ll_row_stride;
     if (planes == 0) return 0;
+    const WlAfbReq r = {x, x_plane_stride, x_row_stride, ll, ll_plane_stride, ll_row_stride, highs, planes, H, W,
+                        {h_w_lo, h_w_hi, h_h_lo, h_h_hi}, Lw, Lh, mode, 0, nullptr, nullptr, stream};
     if (mode == 2 && (H + (H & 1) < Lh - 1 || W + (W & 1) < Lw - 1)) {
         // a level shorter than the filter: the reference folds the wrapped tail only once (dwt/lowlevel.py:146-150),
         // which is not the circular form of the tile kernels - evaluate its formula literally (tiny planes)
         WL_DISPATCH_DTYPE(dtype, {
             typedef typename WlAcc<T>::type A;
             WlDirectArgs<T> a;
-            a.x = (const T*)x; a.highs = nullptr; a.ll = (T*)ll; a.hout = (T*)highs;
-            a.w_lo = (const A*)h_w_lo; a.w_hi = (const A*)h_w_hi; a.h_lo = (const A*)h_h_lo; a.h_hi = (const A*)h_h_hi;
-            a.NC = planes; a.x_ps = st.x_ps; a.ll_ps = st.ll_ps; a.x_rs = st.x_rs; a.ll_rs = st.ll_rs;
-            a.H = H; a.W = W; a.Kh = wl_dwt_coeff_len(H, Lh, mode); a.Kw = wl_dwt_coeff_len(W, Lw, mode);
-            a.Lw = Lw; a.Lh = Lh; a.OH = a.OW = 0;
-            return wl_launch<WlAfbDirect<T> >(a, wl_cdiv64(planes * a.Kh * a.Kw, 256), 0, stream);
+            a.x = (const T*)r.x; a.highs = nullptr; a.ll = (T*)r.ll; a.hout = (T*)r.highs;
+            a.w_lo = (const A*)r.taps.w_lo; a.w_hi = (const A*)r.taps.w_hi; a.h_lo = (const A*)r.taps.h_lo; a.h_hi = (const A*)r.taps.h_hi;
+            a.NC = r.planes; a.x_ps = r.x_ps; a.ll_ps = r.ll_ps; a.x_rs = r.x_rs; a.ll_rs = r.ll_rs;
+            a.H = r.H; a.W = r.W; a.Kh = wl_dwt_coeff_len(r.H, r.Lh, r.mode); a.Kw = wl_dwt_coeff_len(r.W, r.Lw, r.mode);
+            a.Lw = r.Lw; a.Lh = r.Lh; a.OH = a.OW = 0;
+            return wl_launch<WlAfbDirect<T> >(a, wl_cdiv64(r.planes * a.Kh * a.Kw, 256), 0, r.stream);
         });
     }
     if (Lw == Lh && dtype != WL_F64 && !wl_options().generic_only) {
-        int rc = dtype == WL_F32
-                     ? wl_afb_tile_dispatch<float>(st, Lw, x, ll, highs, planes, H, W, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, stream)
-                 : dtype == WL_F16
-                     ? wl_afb_tile_dispatch<wl_half>(st, Lw, x, ll, highs, planes, H, W, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, stream)
-                 : dtype == WL_BF16
-                     ? wl_afb_tile_dispatch<wl_bf16>(st, Lw, x, ll, highs, planes, H, W, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, stream)
-                     : WL_ERR_DTYPE;
+        int rc = dtype == WL_F32    ? wl_afb_tile_dispatch<float>(r)
+                 : dtype == WL_F16  ? wl_afb_tile_dispatch<wl_half>(r)
+                 : dtype == WL_BF16 ? wl_afb_tile_dispatch<wl_bf16>(r)
+                                    : WL_ERR_DTYPE;
         if (rc != WL_ERR_UNSUPPORTED) return rc;
     }
-    WL_DISPATCH_DTYPE(dtype, return wl_afb2d_generic<T>(st, x, ll, highs, planes, H, W, h_w_lo, h_w_hi, Lw,
-                                                        h_h_lo, h_h_hi, Lh, mode, stream));
+    WL_DISPATCH_DTYPE(dtype, return wl_afb2d_generic<T>(r));
     return 0;
 }
 
@@ -224,17 +205,15 @@ extern "C" int wl_dwt2d_analysis(const void* x, void* ll, void* highs, int dtype
 
 // ---- DWT synthesis -----------------------------------------------------------------------------
 template <typename T>
-static int wl_sfb2d_generic(const void* ll, int64_t ll_ps, int ll_rs, const void* highs, void* y,
-                            int64_t planes, int Kh, int Kw, int OH, int OW, const void* gwl,
-                            const void* gwh, int Lw, const void* ghl, const void* ghh, int Lh, int mode,
-                            void* stream) {
+static int wl_sfb2d_generic(const WlSfbReq& r) {
     typedef typename WlAcc<T>::type A;
+    const int OH = r.OH, OW = r.OW, Lw = r.Lw, Lh = r.Lh;
     WlSfb2dArgs<T> a;
-    a.ll = (const T*)ll; a.highs = (const T*)highs; a.y = (T*)y;
-    a.g_w_lo = (const A*)gwl; a.g_w_hi = (const A*)gwh; a.g_h_lo = (const A*)ghl; a.g_h_hi = (const A*)ghh;
-    a.NC = planes; a.ll_plane_stride = ll_ps; a.ll_row_stride = ll_rs;
-    a.Kh = Kh; a.Kw = Kw; a.OH = OH; a.OW = OW; a.Lw = Lw; a.Lh = Lh;
-    a.circ = (mode == 2);
+    a.ll = (const T*)r.ll; a.highs = (const T*)r.highs; a.y = (T*)r.y;
+    a.g_w_lo = (const A*)r.taps.w_lo; a.g_w_hi = (const A*)r.taps.w_hi; a.g_h_lo = (const A*)r.taps.h_lo; a.g_h_hi = (const A*)r.taps.h_hi;
+    a.NC = r.planes; a.ll_plane_stride = r.ll_ps; a.ll_row_stride = r.ll_rs;
+    a.Kh = r.Kh; a.Kw = r.Kw; a.OH = OH; a.OW = OW; a.Lw = Lw; a.Lh = Lh;
+    a.circ = (r.mode == 2);
     a.sw = a.circ ? Lw / 2 - 1 : Lw - 2;
     a.sh = a.circ ? Lh / 2 - 1 : Lh - 2;
     int TH = 16, TW = 64;
@@ -247,39 +226,33 @@ static int wl_sfb2d_generic(const void* ll, int64_t ll_ps, int ll_rs, const void
         if (TW > 16) TW /= 2; else TH /= 2;
     }
     a.tiles_x = wl_cdiv(OW, TW); a.tiles_y = wl_cdiv(OH, TH);
-    return wl_launch<WlSfb2dTile<T> >(a, planes * a.tiles_x * a.tiles_y, wl_sfb2d_tile_lds(a), stream);
+    return wl_launch<WlSfb2dTile<T> >(a, r.planes * a.tiles_x * a.tiles_y, wl_sfb2d_tile_lds(a), r.stream);
 }
 
 template <typename T, int LT, int SODD>
-static int wl_sfb_tile_launch(const void* ll, int64_t ll_ps, int ll_rs, const void* highs, void* y,
-                              int64_t planes, int Kh, int Kw, int OH, int OW, const void* gwl, const void* gwh,
-                              const void* ghl, const void* ghh, int mode, void* stream) {
+static int wl_sfb_tile_launch(const WlSfbReq& r) {
     typedef WlSfbTile<T, LT, SODD> K;
     WlSfbTileArgs<T> a;
-    a.ll = (const T*)ll; a.highs = (const T*)highs; a.y = (T*)y;
-    a.g_w_lo = (const float*)gwl; a.g_w_hi = (const float*)gwh;
-    a.g_h_lo = (const float*)ghl; a.g_h_hi = (const float*)ghh;
-    a.NC = planes; a.ll_plane_stride = ll_ps; a.ll_row_stride = ll_rs;
-    a.Kh = Kh; a.Kw = Kw; a.OH = OH; a.OW = OW;
-    a.circ = (mode == 2);
+    a.ll = (const T*)r.ll; a.highs = (const T*)r.highs; a.y = (T*)r.y;
+    a.g_w_lo = (const float*)r.taps.w_lo; a.g_w_hi = (const float*)r.taps.w_hi;
+    a.g_h_lo = (const float*)r.taps.h_lo; a.g_h_hi = (const float*)r.taps.h_hi;
+    a.NC = r.planes; a.ll_plane_stride = r.ll_ps; a.ll_row_stride = r.ll_rs;
+    a.Kh = r.Kh; a.Kw = r.Kw; a.OH = r.OH; a.OW = r.OW;
+    a.circ = (r.mode == 2);
     a.s = a.circ ? LT / 2 - 1 : LT - 2;
-    a.tiles_x = wl_cdiv(OW, K::TW); a.tiles_y = wl_cdiv(OH, K::TH);
-    a.nblocks = planes * a.tiles_x * a.tiles_y;   // XCD-aware remap: halo rows meet in one L2
-    return wl_launch<K>(a, planes * a.tiles_x * a.tiles_y, (size_t)K::kLdsFloats * sizeof(float), stream);
+    a.tiles_x = wl_cdiv(r.OW, K::TW); a.tiles_y = wl_cdiv(r.OH, K::TH);
+    a.nblocks = r.planes * a.tiles_x * a.tiles_y;   // XCD-aware remap: halo rows meet in one L2
+    return wl_launch<K>(a, r.planes * a.tiles_x * a.tiles_y, (size_t)K::kLdsFloats * sizeof(float), r.stream);
 }
 
 template <typename T>
-static int wl_sfb_tile_dispatch(int L, const void* ll, int64_t ll_ps, int ll_rs, const void* highs, void* y,
-                                int64_t planes, int Kh, int Kw, int OH, int OW, const void* gwl,
-                                const void* gwh, const void* ghl, const void* ghh, int mode, void* stream) {
-    if ((int64_t)OH * OW >= (1LL << 30) || ll_ps >= (1LL << 30) || (int64_t)Kh * ll_rs >= (1LL << 30))
+static int wl_sfb_tile_dispatch(const WlSfbReq& r) {   // (Lw == Lh)
+    if ((int64_t)r.OH * r.OW >= (1LL << 30) || r.ll_ps >= (1LL << 30) || (int64_t)r.Kh * r.ll_rs >= (1LL << 30))
         return WL_ERR_UNSUPPORTED;
 #define WL_CASE(LT_)                                                                                                     \
     case LT_:                                                                                                            \
-        return ((mode == 2 ? LT_ / 2 - 1 : LT_ - 2) & 1)                                                                 \
-                   ? wl_sfb_tile_launch<T, LT_, 1>(ll, ll_ps, ll_rs, highs, y, planes, Kh, Kw, OH, OW, gwl, gwh, ghl, ghh, mode, stream) \
-                   : wl_sfb_tile_launch<T, LT_, 0>(ll, ll_ps, ll_rs, highs, y, planes, Kh, Kw, OH, OW, gwl, gwh, ghl, ghh, mode, stream)
-    switch (L) {
+        return ((r.mode == 2 ? LT_ / 2 - 1 : LT_ - 2) & 1) ? wl_sfb_tile_launch<T, LT_, 1>(r) : wl_sfb_tile_launch<T, LT_, 0>(r)
+    switch (r.Lw) {
         // (14 and 18 taps - db7 / sym7, db9 / sym9 - since round 5: without an instantiation every narrow level of theirs fell to the
         // run-time-tap kernel, 0.73 ms for a 128 x 3 x 512 x 512 db7 forward against 0.31 ms)
         WL_CASE(2); WL_CASE(4); WL_CASE(6); WL_CASE(8); WL_CASE(10); WL_CASE(12); WL_CASE(14); WL_CASE(16); WL_CASE(18); WL_CASE(20);
@@ -298,34 +271,28 @@ extern "C" int wl_dwt2d_synthesis(const void* ll, int64_t ll_plane_stride, int l
     const int fullW = mode == 2 ? 2 * Kw : 2 * Kw - Lw + 2;
     if (planes < 0 || Kh < 1 || Kw < 1 || OH < 1 || OW < 1 || OH > fullH || OW > fullW) return WL_ERR_SHAPE;
     if (planes == 0) return 0;
+    const WlSfbReq r = {ll, ll_plane_stride, ll_row_stride, highs, y, planes, Kh, Kw, OH, OW,
+                        {g_w_lo, g_w_hi, g_h_lo, g_h_hi}, Lw, Lh, mode, 0, nullptr, nullptr, stream};
     if (mode == 2 && (2 * Kh < Lh - 2 || 2 * Kw < Lw - 2)) {
         // fewer outputs than taps: the reference's single fold (dwt/lowlevel.py:256-260), evaluated literally
         WL_DISPATCH_DTYPE(dtype, {
             typedef typename WlAcc<T>::type A;
             WlDirectArgs<T> a;
-            a.x = (const T*)ll; a.highs = (const T*)highs; a.ll = (T*)y; a.hout = nullptr;
-            a.w_lo = (const A*)g_w_lo; a.w_hi = (const A*)g_w_hi; a.h_lo = (const A*)g_h_lo; a.h_hi = (const A*)g_h_hi;
-            a.NC = planes; a.x_ps = ll_plane_stride; a.ll_ps = 0; a.x_rs = ll_row_stride; a.ll_rs = 0;
-            a.H = a.W = 0; a.Kh = Kh; a.Kw = Kw; a.Lw = Lw; a.Lh = Lh; a.OH = OH; a.OW = OW;
-            return wl_launch<WlSfbDirect<T> >(a, wl_cdiv64(planes * OH * OW, 256), 0, stream);
+            a.x = (const T*)r.ll; a.highs = (const T*)r.highs; a.ll = (T*)r.y; a.hout = nullptr;
+            a.w_lo = (const A*)r.taps.w_lo; a.w_hi = (const A*)r.taps.w_hi; a.h_lo = (const A*)r.taps.h_lo; a.h_hi = (const A*)r.taps.h_hi;
+            a.NC = r.planes; a.x_ps = r.ll_ps; a.ll_ps = 0; a.x_rs = r.ll_rs; a.ll_rs = 0;
+            a.H = a.W = 0; a.Kh = r.Kh; a.Kw = r.Kw; a.Lw = r.Lw; a.Lh = r.Lh; a.OH = r.OH; a.OW = r.OW;
+            return wl_launch<WlSfbDirect<T> >(a, wl_cdiv64(r.planes * r.OH * r.OW, 256), 0, r.stream);
         });
     }
     if (Lw == Lh && dtype != WL_F64 && !wl_options().generic_only) {
-        int rc = dtype == WL_F32
-                     ? wl_sfb_tile_dispatch<float>(Lw, ll, ll_plane_stride, ll_row_stride, highs, y, planes, Kh, Kw,
-                                                   OH, OW, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, stream)
-                 : dtype == WL_F16
-                     ? wl_sfb_tile_dispatch<wl_half>(Lw, ll, ll_plane_stride, ll_row_stride, highs, y, planes, Kh,
-                                                     Kw, OH, OW, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, stream)
-                 : dtype == WL_BF16
-                     ? wl_sfb_tile_dispatch<wl_bf16>(Lw, ll, ll_plane_stride, ll_row_stride, highs, y, planes, Kh,
-                                                     Kw, OH, OW, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, stream)
-                     : WL_ERR_DTYPE;
+        int rc = dtype == WL_F32    ? wl_sfb_tile_dispatch<float>(r)
+                 : dtype == WL_F16  ? wl_sfb_tile_dispatch<wl_half>(r)
+                 : dtype == WL_BF16 ? wl_sfb_tile_dispatch<wl_bf16>(r)
+                                    : WL_ERR_DTYPE;
         if (rc != WL_ERR_UNSUPPORTED) return rc;
     }
-    WL_DISPATCH_DTYPE(dtype, return wl_sfb2d_generic<T>(ll, ll_plane_stride, ll_row_stride, highs, y, planes,
-                                                        Kh, Kw, OH, OW, g_w_lo, g_w_hi, Lw, g_h_lo, g_h_hi,
-                                                        Lh, mode, stream));
+    WL_DISPATCH_DTYPE(dtype, return wl_sfb2d_generic<T>(r));
     return 0;
 }
 
@@ -927,13 +894,14 @@ static int wl_afb_small_launch(WlSmallArgs<T>& a, void* stream) {
 }
 
 template <typename T>
-static int wl_afb_small_run(const void* x, void* yl, void* const* yh, int64_t planes, int H, int W, int nlev, const void* hwl,
-                            const void* hwh, const void* hhl, const void* hhh, int L, int mode, void* stream) {
+static int wl_afb_small_run(const WlAfbPyrReq& r) {
     const int SZ = (int)sizeof(T);
+    const int64_t planes = r.planes;
+    const int H = r.H, W = r.W, nlev = r.nlev, L = r.L, mode = r.mode;
     WlSmallArgs<T> a;
-    a.x = (const T*)x; a.yl = (T*)yl;
-    for (int j = 0; j < WL_SMALL_MAXLEV; ++j) a.yh[j] = j < nlev ? (T*)yh[j] : nullptr;
-    a.hw_lo = (const float*)hwl; a.hw_hi = (const float*)hwh; a.hh_lo = (const float*)hhl; a.hh_hi = (const float*)hhh;
+    a.x = (const T*)r.x; a.yl = (T*)r.yl;
+    for (int j = 0; j < WL_SMALL_MAXLEV; ++j) a.yh[j] = j < nlev ? (T*)r.yh[j] : nullptr;
+    a.hw_lo = (const float*)r.taps.w_lo; a.hw_hi = (const float*)r.taps.w_hi; a.hh_lo = (const float*)r.taps.h_lo; a.hh_hi = (const float*)r.taps.h_hi;
     a.planes = planes; a.nlev = nlev; a.L = L; a.ext = wl_mode_to_ext(mode);
     a.h[0] = H; a.w[0] = W;
     for (int j = 0; j < WL_SMALL_MAXLEV; ++j) {
@@ -1008,7 +976,7 @@ static int wl_afb_small_run(const void* x, void* yl, void* const* yh, int64_t pl
     a.mid_off = a.buf_off[1] + wl_align_up(G * ll1 * 4, 16);
     a.tap_off = a.mid_off + wl_align_up(G * mid0 * 4, 16);
     a.lds_bytes = a.tap_off + 4 * L * 4;
-    a.vec_ok = ((H * W) % 4 == 0) && ((int64_t)G * H * W * SZ) % 16 == 0 && (uintptr_t)x % 16 == 0;
+    a.vec_ok = ((H * W) % 4 == 0) && ((int64_t)G * H * W * SZ) % 16 == 0 && (uintptr_t)r.x % 16 == 0;
     a.nblocks = (planes + G - 1) / G;                               // groups; a workgroup walks over several when the chip is full
 #ifndef WL_SMALL_WALK
 #define WL_SMALL_WALK 1          // 0: one workgroup per group (A/B builds)
@@ -1020,11 +988,11 @@ static int wl_afb_small_run(const void* x, void* yl, void* const* yh, int64_t pl
         if (a.nblocks > resident) a.nblocks = resident;
     }
     switch (L) {
-        case 2: return wl_afb_small_launch<T, 2>(a, stream);
-        case 4: return wl_afb_small_launch<T, 4>(a, stream);
-        case 6: return wl_afb_small_launch<T, 6>(a, stream);
-        case 8: return wl_afb_small_launch<T, 8>(a, stream);
-        default: return wl_afb_small_launch<T, 0>(a, stream);
+        case 2: return wl_afb_small_launch<T, 2>(a, r.stream);
+        case 4: return wl_afb_small_launch<T, 4>(a, r.stream);
+        case 6: return wl_afb_small_launch<T, 6>(a, r.stream);
+        case 8: return wl_afb_small_launch<T, 8>(a, r.stream);
+        default: return wl_afb_small_launch<T, 0>(a, r.stream);
     }
 }
 
@@ -1036,25 +1004,26 @@ extern "C" int wl_dwt2d_analysis_small(const void* x, void* yl, void* const* yh,
     if (L < 1 || L > WL_MAX_TAPS) return WL_ERR_TAPS;
     if (nlev < 1 || nlev > WL_SMALL_MAXLEV || L > 20) return WL_ERR_UNSUPPORTED;
     if (planes == 0) return 0;
-    if (dtype == WL_F32) return wl_afb_small_run<float>(x, yl, yh, planes, H, W, nlev, h_w_lo, h_w_hi, h_h_lo, h_h_hi, L, mode, stream);
-    if (dtype == WL_F16) return wl_afb_small_run<wl_half>(x, yl, yh, planes, H, W, nlev, h_w_lo, h_w_hi, h_h_lo, h_h_hi, L, mode, stream);
-    if (dtype == WL_BF16) return wl_afb_small_run<wl_bf16>(x, yl, yh, planes, H, W, nlev, h_w_lo, h_w_hi, h_h_lo, h_h_hi, L, mode, stream);
-    return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
+    const WlAfbPyrReq r = {x, (int64_t)H * W, W, yl, yh, planes, H, W, nlev, {h_w_lo, h_w_hi, h_h_lo, h_h_hi}, L, mode,
+                           0, 0, nullptr, nullptr, stream};
+    WL_DISPATCH_FLOAT(dtype, return wl_afb_small_run<T>(r));
 }
 
 template <typename T>
-static int wl_sfb_small_run(const void* yl, int yl_h, int yl_w, const void* const* yh, const int* Kh, const int* Kw, void* y,
-                            int64_t planes, int nlev, const void* gwl, const void* gwh, const void* ghl, const void* ghh, int L,
-                            int mode, void* stream) {
+static int wl_sfb_small_run(const WlSfbPyrReq& r) {
+    const int64_t planes = r.planes;
+    const int yl_h = r.yl_h, yl_w = r.yl_w, nlev = r.nlev, L = r.L, mode = r.mode;
+    const int* const Kh = r.Kh; const int* const Kw = r.Kw;
+    void* const stream = r.stream;
     WlSmallSynArgs<T> a;
-    a.yl = (const T*)yl; a.y = (T*)y; a.planes = planes; a.nlev = nlev; a.L = L; a.per = mode == 2;
-    a.gw_lo = (const float*)gwl; a.gw_hi = (const float*)gwh; a.gh_lo = (const float*)ghl; a.gh_hi = (const float*)ghh;
+    a.yl = (const T*)r.yl; a.y = (T*)r.y; a.planes = planes; a.nlev = nlev; a.L = L; a.per = mode == 2;
+    a.gw_lo = (const float*)r.taps.w_lo; a.gw_hi = (const float*)r.taps.w_hi; a.gh_lo = (const float*)r.taps.h_lo; a.gh_hi = (const float*)r.taps.h_hi;
     a.llh = yl_h; a.llw = yl_w;
     int hsum = 0, b[2] = {yl_h * yl_w, 1}, mid0 = 1, most = 1;
     int sh = yl_h, sw = yl_w;                                       // size of the ll a level receives
     for (int j = 0; j < WL_SMALL_MAXLEV; ++j) { a.yh[j] = nullptr; a.Kh[j] = a.Kw[j] = a.OH[j] = a.OW[j] = 1; a.mg_pk[j] = a.mg_k[j] = a.mg_pq[j] = a.mg_q[j] = 0; a.h_off[j] = 0; }
     for (int j = nlev - 1; j >= 0; --j) {
-        a.yh[j] = (const T*)yh[j];
+        a.yh[j] = (const T*)r.yh[j];
         a.Kh[j] = Kh[j]; a.Kw[j] = Kw[j];
         if (Kh[j] < 1 || Kw[j] < 1) return WL_ERR_SHAPE;
         // the lowpass a level receives is its high-pass size or one larger (then the surplus row / column is dropped: 'unpad')
@@ -1116,10 +1085,9 @@ extern "C" int wl_dwt2d_synthesis_small(const void* yl, int yl_h, int yl_w, cons
     if (L < 1 || L > WL_MAX_TAPS) return WL_ERR_TAPS;
     if (nlev < 1 || nlev > WL_SMALL_MAXLEV || L > 20 || (L & 1)) return WL_ERR_UNSUPPORTED;
     if (planes == 0) return 0;
-    if (dtype == WL_F32) return wl_sfb_small_run<float>(yl, yl_h, yl_w, yh, Kh, Kw, y, planes, nlev, g_w_lo, g_w_hi, g_h_lo, g_h_hi, L, mode, stream);
-    if (dtype == WL_F16) return wl_sfb_small_run<wl_half>(yl, yl_h, yl_w, yh, Kh, Kw, y, planes, nlev, g_w_lo, g_w_hi, g_h_lo, g_h_hi, L, mode, stream);
-    if (dtype == WL_BF16) return wl_sfb_small_run<wl_bf16>(yl, yl_h, yl_w, yh, Kh, Kw, y, planes, nlev, g_w_lo, g_w_hi, g_h_lo, g_h_hi, L, mode, stream);
-    return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
+    const WlSfbPyrReq r = {yl, (int64_t)yl_h * yl_w, yl_w, yl_h, yl_w, yh, Kh, Kw, y, planes, nlev,
+                           {g_w_lo, g_w_hi, g_h_lo, g_h_hi}, L, mode, 0, 0, nullptr, nullptr, stream};
+    WL_DISPATCH_FLOAT(dtype, return wl_sfb_small_run<T>(r));
 }
 
 // ---- one level of the stationary transform (wl_swt2d.h; reference dwt/lowlevel.py:475-521, :175-223) ----

@@ -113,14 +113,6 @@ extern "C" int wl_dtcwt_inv_level21(const void* ll2, int64_t ll2_plane_stride, i
     if (mode != 1) return WL_ERR_UNSUPPORTED;                   // symmetric (level 1 of the other modes pads with zeros: per-level kernels)
     if (planes == 0) return 0;
     if (wl_streaming_off()) return WL_ERR_UNSUPPORTED;
-    if (dtype == WL_F32)
-        return wl_dtinv21_any<float>(ll2, ll2_plane_stride, ll2_row_stride, highs2, highs1, y, planes, H, W, g0o, L0, g1o, L1,
-                                     g0a, g0b, g1a, g1b, LQ, policy, stream);
-    if (dtype == WL_F16)
-        return wl_dtinv21_any<wl_half>(ll2, ll2_plane_stride, ll2_row_stride, highs2, highs1, y, planes, H, W, g0o, L0, g1o, L1,
-                                       g0a, g0b, g1a, g1b, LQ, policy, stream);
-    if (dtype == WL_BF16)
-        return wl_dtinv21_any<wl_bf16>(ll2, ll2_plane_stride, ll2_row_stride, highs2, highs1, y, planes, H, W, g0o, L0, g1o, L1,
-                                       g0a, g0b, g1a, g1b, LQ, policy, stream);
-    return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
+    WL_DISPATCH_FLOAT(dtype, return wl_dtinv21_any<T>(ll2, ll2_plane_stride, ll2_row_stride, highs2, highs1, y, planes, H, W, g0o, L0,
+                                                      g1o, L1, g0a, g0b, g1a, g1b, LQ, policy, stream));
 }

@@ -90,19 +90,15 @@ extern "C" int wl_dwt1d_analysis_fused(const void* x, void* lo, void* const* hig
         base[j] = wl_afb_base(n[j], L, mode);
         if (mode == 2 && n[j] + (n[j] & 1) < L - 1) return WL_ERR_UNSUPPORTED;
     }
-#define WL_FILL(T_)                                                                                     \
-    WlDwt1dArgs<T_> a;                                                                                  \
-    a.x = (const T_*)x; a.lo = (T_*)lo;                                                                 \
-    for (int j = 0; j < WL_DWT1D_MAXJ; ++j) a.hi[j] = j < J ? (T_*)highs[j] : nullptr;                  \
-    a.h0 = (const float*)h0; a.h1 = (const float*)h1; a.rows = rows; a.J = J; a.ext = ext;              \
-    for (int j = 0; j <= WL_DWT1D_MAXJ; ++j) a.n[j] = j <= J ? n[j] : 0;                                \
-    for (int j = 0; j < WL_DWT1D_MAXJ; ++j) a.base[j] = j < J ? base[j] : 0;                            \
-    return wl_dwt1d_fused_any<T_>(a, L, stream);
-    if (dtype == WL_F32) { WL_FILL(float) }
-    if (dtype == WL_F16) { WL_FILL(wl_half) }
-    if (dtype == WL_BF16) { WL_FILL(wl_bf16) }
-#undef WL_FILL
-    return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
+    WL_DISPATCH_FLOAT(dtype, {
+        WlDwt1dArgs<T> a;
+        a.x = (const T*)x; a.lo = (T*)lo;
+        for (int j = 0; j < WL_DWT1D_MAXJ; ++j) a.hi[j] = j < J ? (T*)highs[j] : nullptr;
+        a.h0 = (const float*)h0; a.h1 = (const float*)h1; a.rows = rows; a.J = J; a.ext = ext;
+        for (int j = 0; j <= WL_DWT1D_MAXJ; ++j) a.n[j] = j <= J ? n[j] : 0;
+        for (int j = 0; j < WL_DWT1D_MAXJ; ++j) a.base[j] = j < J ? base[j] : 0;
+        return wl_dwt1d_fused_any<T>(a, L, stream);
+    });
 }
 
 // ---- fused multi-level 1-D synthesis (wl_idwt1d_fused.h) ---------------------------------------------------------------
@@ -163,15 +159,11 @@ extern "C" int wl_dwt1d_synthesis_fused(const void* lo, int n_lo, const void* co
     }
     if (!(n_hi[J - 1] <= n_lo && n_lo <= n_hi[J - 1] + 1)) return WL_ERR_UNSUPPORTED;
     if ((int64_t)rows * out_len >= (1LL << 40)) return WL_ERR_UNSUPPORTED;
-#define WL_FILL(T_)                                                                                     \
-    WlIdwt1dArgs<T_> a;                                                                                 \
-    a.lo = (const T_*)lo; a.y = (T_*)y; a.n_lo = n_lo; a.out_len = out_len;                             \
-    for (int j = 0; j < WL_IDWT1D_MAXJ; ++j) { a.hi[j] = j < J ? (const T_*)highs[j] : nullptr; a.n_hi[j] = j < J ? n_hi[j] : 0; } \
-    a.g0 = (const float*)g0; a.g1 = (const float*)g1; a.rows = rows; a.J = J;                           \
-    return wl_idwt1d_fused_any<T_>(a, L, stream);
-    if (dtype == WL_F32) { WL_FILL(float) }
-    if (dtype == WL_F16) { WL_FILL(wl_half) }
-    if (dtype == WL_BF16) { WL_FILL(wl_bf16) }
-#undef WL_FILL
-    return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
+    WL_DISPATCH_FLOAT(dtype, {
+        WlIdwt1dArgs<T> a;
+        a.lo = (const T*)lo; a.y = (T*)y; a.n_lo = n_lo; a.out_len = out_len;
+        for (int j = 0; j < WL_IDWT1D_MAXJ; ++j) { a.hi[j] = j < J ? (const T*)highs[j] : nullptr; a.n_hi[j] = j < J ? n_hi[j] : 0; }
+        a.g0 = (const float*)g0; a.g1 = (const float*)g1; a.rows = rows; a.J = J;
+        return wl_idwt1d_fused_any<T>(a, L, stream);
+    });
 }

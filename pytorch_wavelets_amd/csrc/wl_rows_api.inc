@@ -77,14 +77,6 @@ static int wl_rows_plan_segment(const WlRowsArgs<T>& a, WlRowsSeg& sg, int LT, i
     return 0;
 }
 
-// The input planes of the fused analysis: (NC, H, W) through a plane stride and a row pitch (elements).  The loaders bring a row in
-// as 16-byte pieces, so rows start on 16-byte addresses (pitch and plane stride whole pieces); a row whose WIDTH is no whole number
-// of pieces (the odd-width LL of a strip-kernel level: 515 columns below a 1024-wide image) ends inside its last piece - the cells
-// behind it land in the ring's right halo cells and are overwritten there (mirrored samples, or zeros in zero mode) before any
-// lane reads them.  The caller owns pitch - W readable elements behind every row (ops.afb2d_stream pads its ll for that).
-struct WlSrc { const void* p; int64_t ps; int rs; };
-
-
 // Geometry, LDS layout and wave roles of the streaming kernel, the segments the planes are processed in, and a host
 // simulation of each segment's schedule.  strips: 0 = cut as many planes in two as it takes to fill whole rounds of
 // the chip, 1 = whole planes only, 2 = cut every plane (tests).
@@ -100,13 +92,13 @@ static int wl_decline_trace(int n, int line) {
 #define WL_DECLINE(n) wl_decline_trace(n, __LINE__)
 #endif
 template <typename T, int LT, int PPR, int SAME = 0, int LAT = 0, int ODD = 0, int NP2 = 0>
-static int wl_afb_rows_launch(WlSrc x, void* yl, void* const* yh, int64_t planes, int H, int W, int nlev,
-                              const void* hwl, const void* hwh, const void* hhl, const void* hhh, int mode,
-                              int strips, void* stream, const float* lat, int guard = 0, int what = 0) {
+static int wl_afb_rows_launch(const WlAfbPyrReq& r, const float* lat, int guard = 0, int what = 0) {
     // what: 0 = launch, 1 = dry run (every check, no launch), 2 = launch as the armed fallback of a hinted launch
     // lat: device scratch with WlTapPrep's verdict (+ the column lattice for LAT = 1), or null (the guard compares the taps)
     typedef WlAfbRows<T, LT, PPR, WL_ROWS_DEPTH, SAME, LAT, ODD, NP2> K;
     const int WARM = (LT - 2) / 2;
+    const int64_t planes = r.planes;
+    const int H = r.H, W = r.W, nlev = r.nlev, mode = r.mode, strips = r.strips;
     WlRowsArgs<T> a;
     a.ext = wl_mode_to_ext(mode);
     const bool per = a.ext == WL_EXT_PER;
@@ -114,10 +106,10 @@ static int wl_afb_rows_launch(WlSrc x, void* yl, void* const* yh, int64_t planes
     // several levels: zero / symmetric / reflect (single-fold rows above / below the plane) and, round 6, periodization (those rows
     // are computed: see WlRowsSched::src_row); `periodic` (mode 6: the wrap of an EXPANSIVE transform) stays level by level
     if (nlev > 1 && !(a.ext == WL_EXT_ZERO || a.ext == WL_EXT_SYM || a.ext == WL_EXT_REFL || per)) return WL_DECLINE(2);
-    if ((int64_t)H * x.rs >= (1LL << 30) || x.rs < W) return WL_DECLINE(3);   // 32-bit in-plane offsets
-    // level-1 rows arrive by 16-byte LDS-DMA pieces: every row starts on a 16-byte address (see WlSrc for a ragged last piece)
-    if ((x.rs * sizeof(T)) % 16 != 0 || (x.ps * sizeof(T)) % 16 != 0 || (uintptr_t)x.p % 16 != 0 || wl_cdiv(W * (int)sizeof(T), 1024) != PPR) return WL_DECLINE(4);
-    if ((W * sizeof(T)) % 16 != 0 && wl_align_up(W * (int)sizeof(T), 16) > x.rs * (int)sizeof(T)) return WL_DECLINE(5);   // the last piece must lie inside the pitch
+    if ((int64_t)H * r.x_rs >= (1LL << 30) || r.x_rs < W) return WL_DECLINE(3);   // 32-bit in-plane offsets
+    // level-1 rows arrive by 16-byte LDS-DMA pieces: every row starts on a 16-byte address (see WlAfbPyrReq for a ragged last piece)
+    if ((r.x_rs * sizeof(T)) % 16 != 0 || (r.x_ps * sizeof(T)) % 16 != 0 || (uintptr_t)r.x % 16 != 0 || wl_cdiv(W * (int)sizeof(T), 1024) != PPR) return WL_DECLINE(4);
+    if ((W * sizeof(T)) % 16 != 0 && wl_align_up(W * (int)sizeof(T), 16) > r.x_rs * (int)sizeof(T)) return WL_DECLINE(5);   // the last piece must lie inside the pitch
     a.base = wl_afb_base(W, LT, mode);   // the same for every level and both axes (depends on L and mode only)
     if ((a.base & 1) != ODD) return WL_DECLINE(6);   // periodization with L % 4 == 0: the samples sit on odd cells (the ODD instantiations)
     a.nlev = nlev;
@@ -251,7 +243,7 @@ static int wl_afb_rows_launch(WlSrc x, void* yl, void* const* yh, int64_t planes
         // exactly (NP2: the lattice variants of 12 taps and more and their armed two-bank fallbacks, even `base`)
         if constexpr (!NP2 && !ODD && LT >= 12 && ((SAME && LAT) || (!SAME && !LAT))) {
             if (off > 80 * 1024 && nlev > 1)
-                return wl_afb_rows_launch<T, LT, PPR, SAME, LAT, ODD, 1>(x, yl, yh, planes, H, W, nlev, hwl, hwh, hhl, hhh, mode, strips, stream, lat, guard, what);
+                return wl_afb_rows_launch<T, LT, PPR, SAME, LAT, ODD, 1>(r, lat, guard, what);
         }
         if (off > 80 * 1024) return WL_DECLINE(15);            // two workgroups per CU
     }
@@ -309,16 +301,16 @@ static int wl_afb_rows_launch(WlSrc x, void* yl, void* const* yh, int64_t planes
         for (sub = 0; sub < pp; ++sub)
             for (int l = 0; l < WL_ROWS_LOADERS; ++l) place(-1, l, 4 / WL_ROWS_LOADERS);
     }
-    a.x = (const T*)x.p; a.ll = (T*)yl;
-    for (int j = 0; j < nlev; ++j) a.yh[j] = (T*)yh[j];
-    a.h_w_lo = (const float*)hwl; a.h_w_hi = (const float*)hwh;
-    a.h_h_lo = (const float*)hhl; a.h_h_hi = (const float*)hhh;
-    a.NC = planes; a.x_ps = x.ps; a.x_rs = x.rs;
+    a.x = (const T*)r.x; a.ll = (T*)r.yl;
+    for (int j = 0; j < nlev; ++j) a.yh[j] = (T*)r.yh[j];
+    a.h_w_lo = (const float*)r.taps.w_lo; a.h_w_hi = (const float*)r.taps.w_hi;
+    a.h_h_lo = (const float*)r.taps.h_lo; a.h_h_hi = (const float*)r.taps.h_hi;
+    a.NC = planes; a.x_ps = r.x_ps; a.x_rs = r.x_rs;
     a.ll_ps = (int64_t)a.g[nlev - 1].Kh * a.g[nlev - 1].Kw; a.ll_rs = a.g[nlev - 1].Kw;
     a.guard = guard;
     a.lat = lat;
     if (what == 1) return 0;
-    return what == 2 ? wl_launch_armed<K>(a, units + ncut, (size_t)off, stream) : wl_launch<K>(a, units + ncut, (size_t)off, stream);
+    return what == 2 ? wl_launch_armed<K>(a, units + ncut, (size_t)off, r.stream) : wl_launch<K>(a, units + ncut, (size_t)off, r.stream);
 }
 
 // One tap count.  Up to 12 taps: the one-bank variant (SAME) when both axes are handed the same device buffers (proven: no check),
@@ -333,54 +325,33 @@ static int wl_afb_rows_launch(WlSrc x, void* yl, void* const* yh, int64_t planes
 // ODD = 1: the instantiations for an odd `base` (periodization with L % 4 == 0, wl_dwt_rows.h): the two-bank direct form up to 12
 // taps, the lattice variant from 12 taps on (no SAME-only variant: one more instantiation per shape for biorthogonal 12-tap banks).
 template <typename T, int LT, int PPR, int ODD = 0>
-static int wl_afb_rows_pick(WlSrc x, void* yl, void* const* yh, int64_t planes, int H, int W, int nlev,
-                            const void* hwl, const void* hwh, const void* hhl, const void* hhh, int mode, int strips,
-                            void* stream, int hints, float* scratch, int* tstate) {
-    const bool same_hint = (hints & 1) != 0, qmf_hint = (hints & 2) != 0;
-#define WL_ARGS x, yl, yh, planes, H, W, nlev, hwl, hwh, hhl, hhh, mode, strips, stream, (const float*)nullptr
-#define WL_ARGS_L x, yl, yh, planes, H, W, nlev, hwl, hwh, hhl, hhh, mode, strips, stream, scratch
+static int wl_afb_rows_pick(const WlAfbPyrReq& r) {
+    const bool same_hint = (r.hints & 1) != 0, qmf_hint = (r.hints & 2) != 0;
+    const float* const none = nullptr;
     if constexpr (LT >= WL_ROWS_LAT_MIN) {
-        if (same_hint && qmf_hint && scratch) {
-            int rc = wl_afb_rows_launch<T, LT, PPR, 0, 0, ODD>(WL_ARGS_L, 2, 1);   // the fallback's own checks first (it must not decline later)
-            if (rc != 0) return rc;
-            rc = wl_afb_rows_launch<T, LT, PPR, 1, 1, ODD>(WL_ARGS_L, 1, 1);
-            if (rc != 0) return rc;
-            WlTapPrepArgs p;
-            p.h_w_lo = (const float*)hwl; p.h_w_hi = (const float*)hwh; p.h_h_lo = (const float*)hhl; p.h_h_hi = (const float*)hhh;
-            p.out = scratch; p.L = LT; p.syn = 0; p.same = 1;
-            p.tol = sizeof(T) == 2 ? 0x1p-12f : 0x1p-22f;
-            // (*tstate: this library already examined exactly these banks into this scratch WITH the same-banks check - bits 0 and 1)
-            rc = wl_tap_examined(tstate, 3) ? 0 : wl_launch_aux<WlTapPrep<LT> >(p, 1, 0, stream);
-            if (rc != 0) return rc;
-            wl_tap_mark(tstate, 3);
-            rc = wl_afb_rows_launch<T, LT, PPR, 1, 1, ODD>(WL_ARGS_L, 1, 0);
-            if (rc != 0) return rc;
-            return wl_afb_rows_launch<T, LT, PPR, 0, 0, ODD>(WL_ARGS_L, 2, 2);
-        }
+        if (same_hint && qmf_hint && r.scratch)
+            return wl_lattice_launch<LT>([&](int guard, int what) { return wl_afb_rows_launch<T, LT, PPR, 0, 0, ODD>(r, r.scratch, guard, what); },
+                                         [&](int guard, int what) { return wl_afb_rows_launch<T, LT, PPR, 1, 1, ODD>(r, r.scratch, guard, what); },
+                                         r.taps, 0, 1, sizeof(T), r.scratch, r.tstate, 3, r.stream);
     }
     if constexpr (LT > 12) return WL_ERR_UNSUPPORTED;          // (no direct-form fused kernel above 12 taps)
     else {
         if constexpr (LT >= WL_ROWS_SAME_MIN && !ODD) {
-            if (hwl == hhl && hwh == hhh) return wl_afb_rows_launch<T, LT, PPR, 1>(WL_ARGS);
-            if (same_hint) WL_GUARDED_PAIR((wl_afb_rows_launch<T, LT, PPR, 1>), (wl_afb_rows_launch<T, LT, PPR, 0>), WL_ARGS);
+            if (r.taps.w_lo == r.taps.h_lo && r.taps.w_hi == r.taps.h_hi) return wl_afb_rows_launch<T, LT, PPR, 1>(r, none);
+            if (same_hint) WL_GUARDED_PAIR((wl_afb_rows_launch<T, LT, PPR, 1>), (wl_afb_rows_launch<T, LT, PPR, 0>), r, none);
         }
-        return wl_afb_rows_launch<T, LT, PPR, 0, 0, ODD>(WL_ARGS);
+        return wl_afb_rows_launch<T, LT, PPR, 0, 0, ODD>(r, none);
     }
-#undef WL_ARGS
-#undef WL_ARGS_L
 }
 
 template <typename T>
-static int wl_afb_rows_dispatch(int L, WlSrc x, void* yl, void* const* yh, int64_t planes, int H, int W, int nlev,
-                                const void* hwl, const void* hwh, const void* hhl, const void* hhh, int mode, int strips,
-                                void* stream, int hints, float* scratch, int* tstate) {
-    const int ppr = wl_cdiv(W * (int)sizeof(T), 1024);
-    const bool odd = (wl_afb_base(W, L, mode) & 1) != 0;      // periodization with L % 4 == 0
-#define WL_ARGS x, yl, yh, planes, H, W, nlev, hwl, hwh, hhl, hhh, mode, strips, stream, hints, scratch, tstate
+static int wl_afb_rows_dispatch(const WlAfbPyrReq& r) {
+    const int ppr = wl_cdiv(r.W * (int)sizeof(T), 1024);
+    const bool odd = (wl_afb_base(r.W, r.L, r.mode) & 1) != 0;      // periodization with L % 4 == 0
 #define WL_PICK(LT_, P_)                                                               \
     do {                                                                               \
-        if constexpr (LT_ % 4 == 0) { if (odd) return wl_afb_rows_pick<T, LT_, P_, 1>(WL_ARGS); } \
-        return wl_afb_rows_pick<T, LT_, P_, 0>(WL_ARGS);                               \
+        if constexpr (LT_ % 4 == 0) { if (odd) return wl_afb_rows_pick<T, LT_, P_, 1>(r); } \
+        return wl_afb_rows_pick<T, LT_, P_, 0>(r);                                     \
     } while (0)
 #define WL_CASE(LT_)                                                                   \
     case LT_:                                                                          \
@@ -390,13 +361,12 @@ static int wl_afb_rows_dispatch(int L, WlSrc x, void* yl, void* const* yh, int64
             if (ppr == 3) WL_PICK(LT_, 3);                                             \
         }                                                                              \
         return WL_ERR_UNSUPPORTED
-    switch (L) {
+    switch (r.L) {
         WL_CASE(2); WL_CASE(4); WL_CASE(6); WL_CASE(8); WL_CASE(10); WL_CASE(12); WL_CASE(14); WL_CASE(16); WL_CASE(18); WL_CASE(20);
         default: return WL_ERR_UNSUPPORTED;
     }
 #undef WL_CASE
 #undef WL_PICK
-#undef WL_ARGS
 }
 
 extern "C" int wl_dwt2d_analysis_fused_ex(const void* xp, int64_t x_plane_stride, int x_row_stride, void* yl, void* const* yh,
@@ -405,7 +375,6 @@ extern "C" int wl_dwt2d_analysis_fused_ex(const void* xp, int64_t x_plane_stride
                                           int strips, void* tap_scratch, int* tap_state, void* stream) {
     if (wl_mode_to_ext(mode) < 0) return WL_ERR_MODE;
     if (planes < 0 || H < 1 || W < 1 || x_row_stride < W || x_plane_stride < 0) return WL_ERR_SHAPE;
-    const WlSrc x = {xp, x_plane_stride, x_row_stride};
     if (L < 1 || L > WL_MAX_TAPS) return WL_ERR_TAPS;
     if (mode == 2 && (H + (H & 1) < L - 1 || W + (W & 1) < L - 1)) return WL_ERR_UNSUPPORTED;
     // strips bit 2 (value 4): the caller believes that the row and the column banks hold the same taps (a hint: verified on the
@@ -419,16 +388,10 @@ extern "C" int wl_dwt2d_analysis_fused_ex(const void* xp, int64_t x_plane_stride
     if (strips < 0 || strips > 2) return WL_ERR_UNSUPPORTED;
     // one workgroup per plane (or half plane): pays from about 3/8 of the compute units up (strips == 1 forces the kernel)
     if (strips == 0 && 8 * planes < 3 * wl_num_cus()) return WL_ERR_UNSUPPORTED;   // measured break-even against the tile kernels: 96 planes
-    if (dtype == WL_F32)
-        return planes == 0 ? 0 : wl_afb_rows_dispatch<float>(L, x, yl, yh, planes, H, W, nlev, h_w_lo, h_w_hi,
-                                                            h_h_lo, h_h_hi, mode, strips, stream, hints, (float*)tap_scratch, tap_state);
-    if (dtype == WL_F16)
-        return planes == 0 ? 0 : wl_afb_rows_dispatch<wl_half>(L, x, yl, yh, planes, H, W, nlev, h_w_lo,
-                                                              h_w_hi, h_h_lo, h_h_hi, mode, strips, stream, hints, (float*)tap_scratch, tap_state);
-    if (dtype == WL_BF16)
-        return planes == 0 ? 0 : wl_afb_rows_dispatch<wl_bf16>(L, x, yl, yh, planes, H, W, nlev, h_w_lo,
-                                                              h_w_hi, h_h_lo, h_h_hi, mode, strips, stream, hints, (float*)tap_scratch, tap_state);
-    return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
+    const WlAfbPyrReq r = {xp, x_plane_stride, x_row_stride, yl, yh, planes, H, W, nlev, {h_w_lo, h_w_hi, h_h_lo, h_h_hi}, L, mode,
+                           strips, hints, (float*)tap_scratch, tap_state, stream};
+    // (no planes: nothing to do for a dtype the kernel has, the usual codes for the others)
+    WL_DISPATCH_FLOAT(dtype, return planes == 0 ? 0 : wl_afb_rows_dispatch<T>(r));
 }
 
 // (the entry point of library versions up to 1.x: dense x, no device scratch - so no lattice variant: 14, 16, 20 taps decline)
@@ -467,14 +430,15 @@ static int wl_irows_plan_segment(const WlIRowsArgs<T>& a, WlIRowsSeg& sg, int LT
 
 // Geometry, LDS layout, wave roles, segments and their schedules.  strips as for the analysis kernel.
 template <typename T, int LT, int LAT = 0, int PER = 0>
-static int wl_sfb_rows_launch(const void* yl, int64_t ll_ps, int ll_rs, int yl_h, int yl_w, const void* const* yh,
-                              const int* Kh, const int* Kw, void* y, int64_t planes, int nlev, const void* gwl,
-                              const void* gwh, const void* ghl, const void* ghh, int strips, void* stream,
-                              const float* lat = nullptr, int guard = 0, int what = 0) {
+static int wl_sfb_rows_launch(const WlSfbPyrReq& r, const float* lat = nullptr, int guard = 0, int what = 0) {
     // what: 0 = launch, 1 = dry run (every check, no launch), 2 = launch as the armed fallback of a lattice launch
     // PER: periodization (wl_idwt_rows.h): every level exactly twice the size of the level above, all 2K outputs kept
     typedef WlSfbRows<T, LT, LAT, PER> K;
     const int SZ = (int)sizeof(T), WARM = K::WARM;
+    const int64_t planes = r.planes, ll_ps = r.yl_ps;
+    const int ll_rs = r.yl_rs, yl_h = r.yl_h, yl_w = r.yl_w, nlev = r.nlev, strips = r.strips;
+    const void* const yl = r.yl; const void* const* const yh = r.yh;
+    const int* const Kh = r.Kh; const int* const Kw = r.Kw;
     WlIRowsArgs<T> a;
     if (nlev < 1 || nlev > WL_IROWS_MAXLEV) return WL_ERR_UNSUPPORTED;
     a.nlev = nlev;
@@ -694,13 +658,13 @@ static int wl_sfb_rows_launch(const void* yl, int64_t ll_ps, int ll_rs, int yl_h
     a.nwhole = (int)(units - ncut);
     a.yl = (const T*)yl; a.ll_ps = ll_ps;
     for (int j = 0; j < nlev; ++j) a.yh[j] = (const T*)yh[j];
-    a.y = (T*)y;
-    a.g_w_lo = (const float*)gwl; a.g_w_hi = (const float*)gwh;
-    a.g_h_lo = (const float*)ghl; a.g_h_hi = (const float*)ghh;
+    a.y = (T*)r.y;
+    a.g_w_lo = (const float*)r.taps.w_lo; a.g_w_hi = (const float*)r.taps.w_hi;
+    a.g_h_lo = (const float*)r.taps.h_lo; a.g_h_hi = (const float*)r.taps.h_hi;
     a.NC = planes;
     a.guard = guard; a.lat = lat;
     if (what == 1) return 0;
-    return what == 2 ? wl_launch_armed<K>(a, units + ncut, (size_t)off, stream) : wl_launch<K>(a, units + ncut, (size_t)off, stream);
+    return what == 2 ? wl_launch_armed<K>(a, units + ncut, (size_t)off, r.stream) : wl_launch<K>(a, units + ncut, (size_t)off, r.stream);
 }
 
 // One tap count of the fused synthesis: from WL_IROWS_LAT_MIN taps on (8: the metric's inverse), with both hints (one bank for both axes, quadrature-mirror
@@ -708,45 +672,25 @@ static int wl_sfb_rows_launch(const void* yl, int64_t ll_ps, int ll_rs, int yl_h
 // examination of the banks, the four-bank direct form armed behind it (above 12 taps that form exists as this fallback alone:
 // its four banks of tap pairs do not fit the scalar registers); else the direct form up to 12 taps.
 template <typename T, int LT, int PER = 0>
-static int wl_sfb_rows_pick(const void* yl, int64_t ll_ps, int ll_rs, int yl_h, int yl_w, const void* const* yh,
-                            const int* Kh, const int* Kw, void* y, int64_t planes, int nlev, const void* gwl,
-                            const void* gwh, const void* ghl, const void* ghh, int strips, void* stream, int hints, float* scratch, int* tstate) {
-#define WL_ARGS_ yl, ll_ps, ll_rs, yl_h, yl_w, yh, Kh, Kw, y, planes, nlev, gwl, gwh, ghl, ghh, strips, stream
+static int wl_sfb_rows_pick(const WlSfbPyrReq& r) {
     if constexpr (LT >= WL_IROWS_LAT_MIN) {
-        if ((hints & 3) == 3 && scratch) {
-            int rc = wl_sfb_rows_launch<T, LT, 0, PER>(WL_ARGS_, scratch, 2, 1);   // the fallback's own checks first (it must not decline later)
-            if (rc != 0) return rc;
-            rc = wl_sfb_rows_launch<T, LT, 1, PER>(WL_ARGS_, scratch, 1, 1);
-            if (rc != 0) return rc;
-            WlTapPrepArgs p;
-            p.h_w_lo = (const float*)gwl; p.h_w_hi = (const float*)gwh; p.h_h_lo = (const float*)ghl; p.h_h_hi = (const float*)ghh;
-            p.out = scratch; p.L = LT; p.syn = 1; p.same = 1;
-            p.tol = sizeof(T) == 2 ? 0x1p-12f : 0x1p-22f;
-            rc = wl_tap_examined(tstate, 3) ? 0 : wl_launch_aux<WlTapPrep<LT> >(p, 1, 0, stream);
-            if (rc != 0) return rc;
-            wl_tap_mark(tstate, 3);
-            rc = wl_sfb_rows_launch<T, LT, 1, PER>(WL_ARGS_, scratch, 1, 0);
-            if (rc != 0) return rc;
-            return wl_sfb_rows_launch<T, LT, 0, PER>(WL_ARGS_, scratch, 2, 2);
-        }
+        if ((r.hints & 3) == 3 && r.scratch)
+            return wl_lattice_launch<LT>([&](int guard, int what) { return wl_sfb_rows_launch<T, LT, 0, PER>(r, r.scratch, guard, what); },
+                                         [&](int guard, int what) { return wl_sfb_rows_launch<T, LT, 1, PER>(r, r.scratch, guard, what); },
+                                         r.taps, 1, 1, sizeof(T), r.scratch, r.tstate, 3, r.stream);
     }
     if constexpr (LT > 12) return WL_ERR_UNSUPPORTED;
-    else return wl_sfb_rows_launch<T, LT, 0, PER>(WL_ARGS_);
-#undef WL_ARGS_
+    else return wl_sfb_rows_launch<T, LT, 0, PER>(r);
 }
 
 template <typename T>
-static int wl_sfb_rows_dispatch(int L, const void* yl, int64_t ll_ps, int ll_rs, int yl_h, int yl_w, const void* const* yh,
-                                const int* Kh, const int* Kw, void* y, int64_t planes, int nlev, const void* gwl,
-                                const void* gwh, const void* ghl, const void* ghh, int strips, void* stream, int hints, float* scratch, int* tstate, int per) {
-#define WL_ARGS yl, ll_ps, ll_rs, yl_h, yl_w, yh, Kh, Kw, y, planes, nlev, gwl, gwh, ghl, ghh, strips, stream, hints, scratch, tstate
-#define WL_CASE(LT_) case LT_: return per ? wl_sfb_rows_pick<T, LT_, 1>(WL_ARGS) : wl_sfb_rows_pick<T, LT_, 0>(WL_ARGS)
-    switch (L) {
+static int wl_sfb_rows_dispatch(const WlSfbPyrReq& r) {
+#define WL_CASE(LT_) case LT_: return r.mode == 2 ? wl_sfb_rows_pick<T, LT_, 1>(r) : wl_sfb_rows_pick<T, LT_, 0>(r)   // periodization: the PER instantiations (round 6)
+    switch (r.L) {
         WL_CASE(2); WL_CASE(4); WL_CASE(6); WL_CASE(8); WL_CASE(10); WL_CASE(12); WL_CASE(14); WL_CASE(16); WL_CASE(18); WL_CASE(20);
         default: return WL_ERR_UNSUPPORTED;
     }
 #undef WL_CASE
-#undef WL_ARGS
 }
 
 extern "C" int wl_dwt2d_synthesis_fused_ex(const void* yl, int64_t yl_plane_stride, int yl_row_stride, int yl_h, int yl_w,
@@ -757,7 +701,6 @@ extern "C" int wl_dwt2d_synthesis_fused_ex(const void* yl, int64_t yl_plane_stri
     if (wl_mode_to_ext(mode) < 0) return WL_ERR_MODE;
     if (planes < 0 || yl_h < 1 || yl_w < 1) return WL_ERR_SHAPE;
     if (L < 1 || L > WL_MAX_TAPS) return WL_ERR_TAPS;
-    const int per = mode == 2;                             // periodization: the PER instantiations (round 6)
     // strips bits 2-3, tap_scratch and tap_state as for wl_dwt2d_analysis_fused_ex: the hints (same bank on both axes,
     // quadrature-mirror highpass banks) that select the lattice variant, what the scratch already holds
     if (strips > 15) return WL_ERR_UNSUPPORTED;
@@ -767,16 +710,9 @@ extern "C" int wl_dwt2d_synthesis_fused_ex(const void* yl, int64_t yl_plane_stri
     if (strips < 0 || strips > 2) return WL_ERR_UNSUPPORTED;
     if (strips == 0 && 8 * planes < 3 * wl_num_cus()) return WL_ERR_UNSUPPORTED;   // measured break-even against the tile kernels: 96 planes
     if (planes == 0) return 0;
-    if (dtype == WL_F32)
-        return wl_sfb_rows_dispatch<float>(L, yl, yl_plane_stride, yl_row_stride, yl_h, yl_w, yh, Kh, Kw, y, planes,
-                                           nlev, g_w_lo, g_w_hi, g_h_lo, g_h_hi, strips, stream, hints, (float*)tap_scratch, tap_state, per);
-    if (dtype == WL_F16)
-        return wl_sfb_rows_dispatch<wl_half>(L, yl, yl_plane_stride, yl_row_stride, yl_h, yl_w, yh, Kh, Kw, y, planes,
-                                             nlev, g_w_lo, g_w_hi, g_h_lo, g_h_hi, strips, stream, hints, (float*)tap_scratch, tap_state, per);
-    if (dtype == WL_BF16)
-        return wl_sfb_rows_dispatch<wl_bf16>(L, yl, yl_plane_stride, yl_row_stride, yl_h, yl_w, yh, Kh, Kw, y, planes,
-                                             nlev, g_w_lo, g_w_hi, g_h_lo, g_h_hi, strips, stream, hints, (float*)tap_scratch, tap_state, per);
-    return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
+    const WlSfbPyrReq r = {yl, yl_plane_stride, yl_row_stride, yl_h, yl_w, yh, Kh, Kw, y, planes, nlev,
+                           {g_w_lo, g_w_hi, g_h_lo, g_h_hi}, L, mode, strips, hints, (float*)tap_scratch, tap_state, stream};
+    WL_DISPATCH_FLOAT(dtype, return wl_sfb_rows_dispatch<T>(r));
 }
 
 extern "C" int wl_dwt2d_synthesis_fused(const void* yl, int64_t yl_plane_stride, int yl_row_stride, int yl_h, int yl_w,

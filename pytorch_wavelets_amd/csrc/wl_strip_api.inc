@@ -72,23 +72,23 @@ static void wl_pick_segments(int rows, int64_t units, int wgs_per_cu, int halo, 
 // Strip width, row segments and the LDS layout; declines (WL_ERR_UNSUPPORTED) what the kernel does not cover.
 // policy: 0 = the engine decides whether the launch pays, 1 = force.
 template <typename T, int LT, int QMF = 0, int LAT = 0>
-static int wl_afb_strip_launch(const void* x, int64_t x_ps, int x_rs, void* ll, int64_t ll_ps, int ll_rs, void* highs,
-                               int64_t planes, int H, int W, const void* hwl, const void* hwh, const void* hhl,
-                               const void* hhh, int mode, int policy, void* stream, const float* lat, int guard = 0, int what = 0) {
+static int wl_afb_strip_launch(const WlAfbReq& r, const float* lat, int guard = 0, int what = 0) {
     // what: 0 = launch, 1 = dry run (every check, no launch), 2 = launch as the armed fallback of a hinted launch
     // lat: device scratch with WlTapPrep's verdict (+ the column lattice for LAT = 1), or null (the guard reads the taps)
     typedef WlAfbStrip<T, LT, QMF, LAT> K;
     const int SZ = (int)sizeof(T), A = K::A;
+    const int64_t planes = r.planes, x_ps = r.x_ps, ll_ps = r.ll_ps;
+    const int H = r.H, W = r.W, x_rs = r.x_rs, ll_rs = r.ll_rs;
     WlStripArgs<T> a;
-    a.ext = wl_mode_to_ext(mode);
+    a.ext = wl_mode_to_ext(r.mode);
     a.H = H; a.W = W;
-    a.Kh = wl_coeff_len(H, LT, mode); a.Kw = wl_coeff_len(W, LT, mode);
-    a.base = wl_afb_base(W, LT, mode);
+    a.Kh = wl_coeff_len(H, LT, r.mode); a.Kw = wl_coeff_len(W, LT, r.mode);
+    a.base = wl_afb_base(W, LT, r.mode);
     // the stagers load 4-cell groups at element alignment: any row width and pitch; wrapped groups (periodic /
     // periodization) must be whole groups.  (The LDS-DMA form of the A/B builds needs 16-byte rows and pitches.)
     if (K::wraps(a.ext) && W % 4) return WL_ERR_UNSUPPORTED;
-    if (!WL_STRIP_DIRECT && ((W * SZ) % 16 || (uintptr_t)x % 16 || ((int64_t)x_rs * SZ) % 16 || (x_ps * SZ) % 16)) return WL_ERR_UNSUPPORTED;
-    if ((uintptr_t)x % SZ) return WL_ERR_UNSUPPORTED;
+    if (!WL_STRIP_DIRECT && ((W * SZ) % 16 || (uintptr_t)r.x % 16 || ((int64_t)x_rs * SZ) % 16 || (x_ps * SZ) % 16)) return WL_ERR_UNSUPPORTED;
+    if ((uintptr_t)r.x % SZ) return WL_ERR_UNSUPPORTED;
     if ((int64_t)H * x_rs >= (1LL << 29) || (int64_t)a.Kh * a.Kw >= (1LL << 29) || (int64_t)a.Kh * ll_rs >= (1LL << 29)) return WL_ERR_UNSUPPORTED;
     if (W < 2 * LT || H < 2) return WL_ERR_UNSUPPORTED;       // a mirrored / wrapped halo must come from inside the row, once
     if (a.ext == WL_EXT_SYM || a.ext == WL_EXT_REFL || a.ext == WL_EXT_PERIODIC) {
@@ -167,51 +167,30 @@ static int wl_afb_strip_launch(const void* x, int64_t x_ps, int x_rs, void* ll, 
     // at 128 columns and few planes the tile kernels stay ahead, 0.016 against 0.027 ms)
     const int busy = a.pp * wl_cdiv(wl_cdiv(a.Kw, 2), 64);
     const bool packed = (busy >= WL_STRIP_CWAVES && W >= 128) || (2 * busy >= WL_STRIP_CWAVES && W * SZ >= 1024);
-    if (!(policy & 1) && (nblocks < wl_num_cus() || !(wide || packed))) return WL_ERR_UNSUPPORTED;
-    a.x = (const T*)x; a.ll = (T*)ll; a.highs = (T*)highs;
-    a.h_w_lo = (const float*)hwl; a.h_w_hi = (const float*)hwh; a.h_h_lo = (const float*)hhl; a.h_h_hi = (const float*)hhh;
+    if (!(r.policy & 1) && (nblocks < wl_num_cus() || !(wide || packed))) return WL_ERR_UNSUPPORTED;
+    a.x = (const T*)r.x; a.ll = (T*)r.ll; a.highs = (T*)r.highs;
+    a.h_w_lo = (const float*)r.taps.w_lo; a.h_w_hi = (const float*)r.taps.w_hi; a.h_h_lo = (const float*)r.taps.h_lo; a.h_h_hi = (const float*)r.taps.h_hi;
     a.NC = planes; a.x_ps = x_ps; a.ll_ps = ll_ps; a.x_rs = x_rs; a.ll_rs = ll_rs;
     a.nblocks = nblocks;
-    a.pair_ok = a.Kw % 2 == 0 && ll_rs % 2 == 0 && ll_ps % 2 == 0 && (uintptr_t)ll % (2 * SZ) == 0 && (uintptr_t)highs % (2 * SZ) == 0;
+    a.pair_ok = a.Kw % 2 == 0 && ll_rs % 2 == 0 && ll_ps % 2 == 0 && (uintptr_t)r.ll % (2 * SZ) == 0 && (uintptr_t)r.highs % (2 * SZ) == 0;
     a.guard = guard;
     a.lat = lat;
     if (what == 1) return 0;
-    return what == 2 ? wl_launch_armed<K>(a, nblocks, (size_t)a.lds_bytes, stream) : wl_launch<K>(a, nblocks, (size_t)a.lds_bytes, stream);
+    return what == 2 ? wl_launch_armed<K>(a, nblocks, (size_t)a.lds_bytes, r.stream) : wl_launch<K>(a, nblocks, (size_t)a.lds_bytes, r.stream);
 }
 
-// The lattice variant (wl_lattice.h): WlTapPrep leaves its verdict on the banks + the column lattice in the caller's device
-// scratch, the lattice kernel runs if the verdict is good, the two-bank kernel behind it if not.
+// The lattice variant (wl_lattice_launch): the lattice kernel behind WlTapPrep, the two-bank kernel armed behind it.
 template <typename T, int LT>
-static int wl_afb_strip_lattice(const void* x, int64_t x_ps, int x_rs, void* ll, int64_t ll_ps, int ll_rs, void* highs,
-                                int64_t planes, int H, int W, const void* hwl, const void* hwh, const void* hhl,
-                                const void* hhh, int mode, int policy, void* stream, float* scratch, int* tstate) {
-#define WL_ARGS_ x, x_ps, x_rs, ll, ll_ps, ll_rs, highs, planes, H, W, hwl, hwh, hhl, hhh, mode, policy, stream, scratch
-    int rc = wl_afb_strip_launch<T, LT, 0, 0>(WL_ARGS_, 2, 1);       // the fallback's own checks first (it must not decline later)
-    if (rc != 0) return rc;
-    rc = wl_afb_strip_launch<T, LT, 1, 1>(WL_ARGS_, 1, 1);
-    if (rc != 0) return rc;
-    WlTapPrepArgs p;
-    p.h_w_lo = (const float*)hwl; p.h_w_hi = (const float*)hwh; p.h_h_lo = (const float*)hhl; p.h_h_hi = (const float*)hhh;
-    p.out = scratch; p.L = LT; p.syn = 0; p.same = 0;
-    p.tol = sizeof(T) == 2 ? 0x1p-12f : 0x1p-22f;       // a quarter unit in the last place of float16 storage / float32: wl_lattice.h
-    // (*tstate bit 0: the scratch already holds the verdict on exactly these banks - an earlier level of the same transform, which
-    // THIS library examined: the launcher that runs WlTapPrep sets the bit, nobody else)
-    rc = wl_tap_examined(tstate, 1) ? 0 : wl_launch_aux<WlTapPrep<LT> >(p, 1, 0, stream);
-    if (rc != 0) return rc;
-    wl_tap_mark(tstate, 1);
-    rc = wl_afb_strip_launch<T, LT, 1, 1>(WL_ARGS_, 1, 0);
-    if (rc != 0) return rc;
-    return wl_afb_strip_launch<T, LT, 0, 0>(WL_ARGS_, 2, 2);
-#undef WL_ARGS_
+static int wl_afb_strip_lattice(const WlAfbReq& r) {
+    return wl_lattice_launch<LT>([&](int guard, int what) { return wl_afb_strip_launch<T, LT, 0, 0>(r, r.scratch, guard, what); },
+                                 [&](int guard, int what) { return wl_afb_strip_launch<T, LT, 1, 1>(r, r.scratch, guard, what); },
+                                 r.taps, 0, 0, sizeof(T), r.scratch, r.tstate, 1, r.stream);
 }
 
 template <typename T>
-static int wl_afb_strip_dispatch(int L, const void* x, int64_t x_ps, int x_rs, void* ll, int64_t ll_ps, int ll_rs,
-                                 void* highs, int64_t planes, int H, int W, const void* hwl, const void* hwh,
-                                 const void* hhl, const void* hhh, int mode, int policy, void* stream, float* scratch, int* tstate) {
-#define WL_ARGS x, x_ps, x_rs, ll, ll_ps, ll_rs, highs, planes, H, W, hwl, hwh, hhl, hhh, mode, policy, stream, (const float*)nullptr
-#define WL_ARGS_L x, x_ps, x_rs, ll, ll_ps, ll_rs, highs, planes, H, W, hwl, hwh, hhl, hhh, mode, policy, stream, scratch, tstate
-#define WL_CASE(LT_) case LT_: return wl_afb_strip_launch<T, LT_>(WL_ARGS)
+static int wl_afb_strip_dispatch(const WlAfbReq& r) {   // (Lw == Lh)
+    const float* const none = nullptr;
+#define WL_CASE(LT_) case LT_: return wl_afb_strip_launch<T, LT_>(r, none)
     // policy bit 1 (value 2): the caller vouches for quadrature-mirror highpass banks; from 12 taps on the kernel then derives
     // the (lo, hi) tap pairs from the lowpass bank alone (below that the scalar file holds both banks)
     // (a hint, not a promise: the variant verifies the relation on the device and the two-bank variant stands by behind it)
@@ -221,17 +200,15 @@ static int wl_afb_strip_dispatch(int L, const void* x, int64_t x_ps, int x_rs, v
 #ifndef WL_STRIP_LAT_MIN
 #define WL_STRIP_LAT_MIN 12
 #endif
-#define WL_CASEQ(LT_) case LT_: if (!(policy & 2)) return wl_afb_strip_launch<T, LT_>(WL_ARGS); \
-                                 if constexpr (LT_ >= WL_STRIP_LAT_MIN && LT_ != 18) { if (scratch) return wl_afb_strip_lattice<T, LT_>(WL_ARGS_L); } \
-                                 WL_GUARDED_PAIR((wl_afb_strip_launch<T, LT_, 1>), (wl_afb_strip_launch<T, LT_, 0>), WL_ARGS)
-    switch (L) {
+#define WL_CASEQ(LT_) case LT_: if (!(r.policy & 2)) return wl_afb_strip_launch<T, LT_>(r, none); \
+                                 if constexpr (LT_ >= WL_STRIP_LAT_MIN && LT_ != 18) { if (r.scratch) return wl_afb_strip_lattice<T, LT_>(r); } \
+                                 WL_GUARDED_PAIR((wl_afb_strip_launch<T, LT_, 1>), (wl_afb_strip_launch<T, LT_, 0>), r, none)
+    switch (r.Lw) {
         WL_CASE(2); WL_CASE(4); WL_CASE(6); WL_CASE(8); WL_CASE(10); WL_CASEQ(12); WL_CASEQ(14); WL_CASEQ(16); WL_CASEQ(18); WL_CASEQ(20);
         default: return WL_ERR_UNSUPPORTED;
     }
 #undef WL_CASEQ
 #undef WL_CASE
-#undef WL_ARGS
-#undef WL_ARGS_L
 }
 
 extern "C" int wl_dwt2d_analysis_stream_ex(const void* x, int64_t x_plane_stride, int x_row_stride, void* ll,
@@ -248,16 +225,9 @@ extern "C" int wl_dwt2d_analysis_stream_ex(const void* x, int64_t x_plane_stride
     if (wl_streaming_off()) return WL_ERR_UNSUPPORTED;   // generic_only / no_stream: the callers fall back to the tile / generic kernels
     if (mode == 2 && (H + (H & 1) < L - 1 || W + (W & 1) < L - 1)) return WL_ERR_UNSUPPORTED;   // single-fold corner: direct kernels
     if (planes == 0) return 0;
-    if (dtype == WL_F32)
-        return wl_afb_strip_dispatch<float>(L, x, x_plane_stride, x_row_stride, ll, ll_plane_stride, ll_row_stride, highs,
-                                            planes, H, W, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, policy, stream, (float*)tap_scratch, tap_state);
-    if (dtype == WL_F16)
-        return wl_afb_strip_dispatch<wl_half>(L, x, x_plane_stride, x_row_stride, ll, ll_plane_stride, ll_row_stride, highs,
-                                              planes, H, W, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, policy, stream, (float*)tap_scratch, tap_state);
-    if (dtype == WL_BF16)
-        return wl_afb_strip_dispatch<wl_bf16>(L, x, x_plane_stride, x_row_stride, ll, ll_plane_stride, ll_row_stride, highs,
-                                              planes, H, W, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, policy, stream, (float*)tap_scratch, tap_state);
-    return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
+    const WlAfbReq r = {x, x_plane_stride, x_row_stride, ll, ll_plane_stride, ll_row_stride, highs, planes, H, W,
+                        {h_w_lo, h_w_hi, h_h_lo, h_h_hi}, L, L, mode, policy, (float*)tap_scratch, tap_state, stream};
+    WL_DISPATCH_FLOAT(dtype, return wl_afb_strip_dispatch<T>(r));
 }
 
 // (the entry point of library versions up to 1.x: no device scratch, so the hinted variant of 12 taps and more is the QMF kernel)
@@ -276,13 +246,13 @@ extern "C" int wl_dwt2d_analysis_stream(const void* x, int64_t x_plane_stride, i
 #include "wl_idwt_strip.h"
 
 template <typename T, int LT, int SODD, int QMF = 0, int LAT = 0>
-static int wl_sfb_strip_launch(const void* ll, int64_t ll_ps, int ll_rs, const void* highs, void* y, int64_t planes,
-                               int Kh, int Kw, int OH, int OW, const void* gwl, const void* gwh, const void* ghl,
-                               const void* ghh, int mode, int policy, void* stream, const float* lat, int guard = 0, int what = 0) {
+static int wl_sfb_strip_launch(const WlSfbReq& r, const float* lat, int guard = 0, int what = 0) {
     typedef WlSfbStrip<T, LT, SODD, QMF, LAT> K;
     const int SZ = (int)sizeof(T), A = K::A, HL = LT / 2;
+    const int64_t planes = r.planes, ll_ps = r.ll_ps;
+    const int ll_rs = r.ll_rs, Kh = r.Kh, Kw = r.Kw, OH = r.OH, OW = r.OW;
     WlIStripArgs<T> a;
-    a.per = mode == 2;
+    a.per = r.mode == 2;
     a.Kh = Kh; a.Kw = Kw; a.OH = OH; a.OW = OW;
     a.sw = a.per ? HL - 1 : LT - 2;
     a.sh = a.sw;
@@ -290,8 +260,8 @@ static int wl_sfb_strip_launch(const void* ll, int64_t ll_ps, int ll_rs, const v
     // the stagers load 4-cell groups at element alignment: any row width and pitch; wrapped groups (periodization) must be
     // whole groups.  (The LDS-DMA form of the A/B builds needs 16-byte rows and pitches.)
     if (a.per && Kw % 4) return WL_ERR_UNSUPPORTED;
-    if (!WL_STRIP_DIRECT && ((Kw * SZ) % 16 || (uintptr_t)ll % 16 || (uintptr_t)highs % 16 || ((int64_t)ll_rs * SZ) % 16 || (ll_ps * SZ) % 16)) return WL_ERR_UNSUPPORTED;
-    if ((uintptr_t)ll % SZ || (uintptr_t)highs % SZ) return WL_ERR_UNSUPPORTED;
+    if (!WL_STRIP_DIRECT && ((Kw * SZ) % 16 || (uintptr_t)r.ll % 16 || (uintptr_t)r.highs % 16 || ((int64_t)ll_rs * SZ) % 16 || (ll_ps * SZ) % 16)) return WL_ERR_UNSUPPORTED;
+    if ((uintptr_t)r.ll % SZ || (uintptr_t)r.highs % SZ) return WL_ERR_UNSUPPORTED;
     if ((int64_t)Kh * Kw >= (1LL << 28) || (int64_t)OH * OW >= (1LL << 29) || (int64_t)Kh * ll_rs >= (1LL << 29)) return WL_ERR_UNSUPPORTED;
     if (Kw < LT || Kh < HL) return WL_ERR_UNSUPPORTED;
     // z-row pairs that hold output rows: all of them under periodization, from L/2-1 on otherwise; the crop drops the rest
@@ -348,80 +318,59 @@ static int wl_sfb_strip_launch(const void* ll, int64_t ll_ps, int ll_rs, const v
     // 256 columns, periodization, against the tile kernel: 0.23-0.30 -> 0.14-0.16 ms; tools/gpu_r5p_policy.py)
     const bool wide = WL_ISTRIP_MINW && SZ == 2 ? OW >= WL_ISTRIP_MINW : OW * SZ >= 1024;
     const bool packed = a.pp * wl_cdiv(units, 64) >= WL_STRIP_CWAVES && OW >= 128;
-    if (!(policy & 1) && (nblocks < wl_num_cus() || !(wide || packed) || OW % 4 || (uintptr_t)y % (4 * SZ))) return WL_ERR_UNSUPPORTED;
-    a.ll = (const T*)ll; a.highs = (const T*)highs; a.y = (T*)y;
-    a.g_w_lo = (const float*)gwl; a.g_w_hi = (const float*)gwh; a.g_h_lo = (const float*)ghl; a.g_h_hi = (const float*)ghh;
+    if (!(r.policy & 1) && (nblocks < wl_num_cus() || !(wide || packed) || OW % 4 || (uintptr_t)r.y % (4 * SZ))) return WL_ERR_UNSUPPORTED;
+    a.ll = (const T*)r.ll; a.highs = (const T*)r.highs; a.y = (T*)r.y;
+    a.g_w_lo = (const float*)r.taps.w_lo; a.g_w_hi = (const float*)r.taps.w_hi; a.g_h_lo = (const float*)r.taps.h_lo; a.g_h_hi = (const float*)r.taps.h_hi;
     a.NC = planes; a.ll_ps = ll_ps; a.ll_rs = ll_rs; a.nblocks = nblocks;
-    a.quad_ok = OW % 4 == 0 && (uintptr_t)y % (4 * SZ) == 0;
+    a.quad_ok = OW % 4 == 0 && (uintptr_t)r.y % (4 * SZ) == 0;
     a.guard = guard;
     a.lat = lat;
     if (what == 1) return 0;
-    return what == 2 ? wl_launch_armed<K>(a, nblocks, (size_t)a.lds_bytes, stream) : wl_launch<K>(a, nblocks, (size_t)a.lds_bytes, stream);
+    return what == 2 ? wl_launch_armed<K>(a, nblocks, (size_t)a.lds_bytes, r.stream) : wl_launch<K>(a, nblocks, (size_t)a.lds_bytes, r.stream);
 }
 
-// The lattice variant (wl_lattice.h): WlTapPrep's verdict + the column lattice in the caller's device scratch, the lattice
-// kernel, the two-bank kernel behind it.
+// The lattice variant (wl_lattice_launch): the lattice kernel behind WlTapPrep, the two-bank kernel armed behind it.
 template <typename T, int LT, int SODD>
-static int wl_sfb_strip_lattice(const void* ll, int64_t ll_ps, int ll_rs, const void* highs, void* y, int64_t planes,
-                                int Kh, int Kw, int OH, int OW, const void* gwl, const void* gwh, const void* ghl,
-                                const void* ghh, int mode, int policy, void* stream, float* scratch, int* tstate) {
-#define WL_ARGS_ ll, ll_ps, ll_rs, highs, y, planes, Kh, Kw, OH, OW, gwl, gwh, ghl, ghh, mode, policy, stream, scratch
-    int rc = wl_sfb_strip_launch<T, LT, SODD, 0, 0>(WL_ARGS_, 2, 1);   // the fallback's own checks first (it must not decline later)
-    if (rc != 0) return rc;
-    rc = wl_sfb_strip_launch<T, LT, SODD, 1, 1>(WL_ARGS_, 1, 1);
-    if (rc != 0) return rc;
-    WlTapPrepArgs p;
-    p.h_w_lo = (const float*)gwl; p.h_w_hi = (const float*)gwh; p.h_h_lo = (const float*)ghl; p.h_h_hi = (const float*)ghh;
-    p.out = scratch; p.L = LT; p.syn = 1; p.same = 0;
-    p.tol = sizeof(T) == 2 ? 0x1p-12f : 0x1p-22f;
-    rc = wl_tap_examined(tstate, 1) ? 0 : wl_launch_aux<WlTapPrep<LT> >(p, 1, 0, stream);
-    if (rc != 0) return rc;
-    wl_tap_mark(tstate, 1);
-    rc = wl_sfb_strip_launch<T, LT, SODD, 1, 1>(WL_ARGS_, 1, 0);
-    if (rc != 0) return rc;
-    return wl_sfb_strip_launch<T, LT, SODD, 0, 0>(WL_ARGS_, 2, 2);
-#undef WL_ARGS_
+static int wl_sfb_strip_lattice(const WlSfbReq& r) {
+    return wl_lattice_launch<LT>([&](int guard, int what) { return wl_sfb_strip_launch<T, LT, SODD, 0, 0>(r, r.scratch, guard, what); },
+                                 [&](int guard, int what) { return wl_sfb_strip_launch<T, LT, SODD, 1, 1>(r, r.scratch, guard, what); },
+                                 r.taps, 1, 0, sizeof(T), r.scratch, r.tstate, 1, r.stream);
 }
 
 template <typename T>
-static int wl_sfb_strip_dispatch(int L, const void* ll, int64_t ll_ps, int ll_rs, const void* highs, void* y,
-                                 int64_t planes, int Kh, int Kw, int OH, int OW, const void* gwl, const void* gwh,
-                                 const void* ghl, const void* ghh, int mode, int policy, void* stream, float* scratch, int* tstate) {
-    const int sodd = (mode == 2 ? L / 2 - 1 : L - 2) & 1;
-#define WL_ARGS ll, ll_ps, ll_rs, highs, y, planes, Kh, Kw, OH, OW, gwl, gwh, ghl, ghh, mode, policy, stream, (const float*)nullptr
-#define WL_ARGS_L ll, ll_ps, ll_rs, highs, y, planes, Kh, Kw, OH, OW, gwl, gwh, ghl, ghh, mode, policy, stream, scratch, tstate
+static int wl_sfb_strip_dispatch(const WlSfbReq& r) {   // (Lw == Lh)
+    const int sodd = (r.mode == 2 ? r.Lw / 2 - 1 : r.Lw - 2) & 1;
+    const float* const none = nullptr;
     // policy bit 1 (value 2): the caller vouches for quadrature-mirror highpass banks; from 12 taps on the kernel then derives
     // the highpass tap pairs from the lowpass ones (below that the scalar file holds both).  NOT at 14 taps: that instantiation
     // needs 19 more vector registers than four waves per SIMD leave it and spills them - measured 0.434 against 0.332 ms
     // (float32) and 1.85 against 1.04 ms (float16) for the two-bank kernel with its 13 spilled scalars (tools/gpu_qmf_probe.py)
-    const bool qmf = (policy & 2) != 0;
-#define WL_CASE0(LT_) case LT_: return sodd ? WL_ERR_UNSUPPORTED : wl_sfb_strip_launch<T, LT_, 0>(WL_ARGS)
-#define WL_CASE2(LT_) case LT_: return sodd ? wl_sfb_strip_launch<T, LT_, 1>(WL_ARGS) : wl_sfb_strip_launch<T, LT_, 0>(WL_ARGS)
+    const bool qmf = (r.policy & 2) != 0;
+#define WL_CASE0(LT_) case LT_: return sodd ? WL_ERR_UNSUPPORTED : wl_sfb_strip_launch<T, LT_, 0>(r, none)
+#define WL_CASE2(LT_) case LT_: return sodd ? wl_sfb_strip_launch<T, LT_, 1>(r, none) : wl_sfb_strip_launch<T, LT_, 0>(r, none)
     // (a hint, not a promise: the QMF variant verifies the relation on the device, the two-bank variant stands by behind it)
     // With device scratch from the caller the hinted variant is the LATTICE kernel (wl_lattice.h), also at 14 taps where the
     // QMF variant alone does not pay.
 #define WL_CASE0Q(LT_) case LT_: if (sodd) return WL_ERR_UNSUPPORTED;                                  \
-                                  if (!qmf) return wl_sfb_strip_launch<T, LT_, 0>(WL_ARGS);             \
-                                  if constexpr (LT_ != 18) { if (scratch) return wl_sfb_strip_lattice<T, LT_, 0>(WL_ARGS_L); }   /* (18: see the analysis) */ \
-                                  WL_GUARDED_PAIR((wl_sfb_strip_launch<T, LT_, 0, 1>), (wl_sfb_strip_launch<T, LT_, 0, 0>), WL_ARGS)
+                                  if (!qmf) return wl_sfb_strip_launch<T, LT_, 0>(r, none);             \
+                                  if constexpr (LT_ != 18) { if (r.scratch) return wl_sfb_strip_lattice<T, LT_, 0>(r); }   /* (18: see the analysis) */ \
+                                  WL_GUARDED_PAIR((wl_sfb_strip_launch<T, LT_, 0, 1>), (wl_sfb_strip_launch<T, LT_, 0, 0>), r, none)
 #define WL_CASE0L(LT_) case LT_: if (sodd) return WL_ERR_UNSUPPORTED;                                  \
-                                  if (qmf && scratch) return wl_sfb_strip_lattice<T, LT_, 0>(WL_ARGS_L); \
-                                  return wl_sfb_strip_launch<T, LT_, 0>(WL_ARGS)
-#define WL_CASE2Q(LT_) case LT_: if (!qmf) return sodd ? wl_sfb_strip_launch<T, LT_, 1>(WL_ARGS) : wl_sfb_strip_launch<T, LT_, 0>(WL_ARGS); \
-                                  if (scratch) return sodd ? wl_sfb_strip_lattice<T, LT_, 1>(WL_ARGS_L) : wl_sfb_strip_lattice<T, LT_, 0>(WL_ARGS_L); \
-                                  if (sodd) WL_GUARDED_PAIR((wl_sfb_strip_launch<T, LT_, 1, 1>), (wl_sfb_strip_launch<T, LT_, 1, 0>), WL_ARGS); \
-                                  WL_GUARDED_PAIR((wl_sfb_strip_launch<T, LT_, 0, 1>), (wl_sfb_strip_launch<T, LT_, 0, 0>), WL_ARGS)
-    switch (L) {   // an odd roll (SODD) only exists for periodization with L % 4 == 0
+                                  if (qmf && r.scratch) return wl_sfb_strip_lattice<T, LT_, 0>(r); \
+                                  return wl_sfb_strip_launch<T, LT_, 0>(r, none)
+#define WL_CASE2Q(LT_) case LT_: if (!qmf) return sodd ? wl_sfb_strip_launch<T, LT_, 1>(r, none) : wl_sfb_strip_launch<T, LT_, 0>(r, none); \
+                                  if (r.scratch) return sodd ? wl_sfb_strip_lattice<T, LT_, 1>(r) : wl_sfb_strip_lattice<T, LT_, 0>(r); \
+                                  if (sodd) WL_GUARDED_PAIR((wl_sfb_strip_launch<T, LT_, 1, 1>), (wl_sfb_strip_launch<T, LT_, 1, 0>), r, none); \
+                                  WL_GUARDED_PAIR((wl_sfb_strip_launch<T, LT_, 0, 1>), (wl_sfb_strip_launch<T, LT_, 0, 0>), r, none)
+    switch (r.Lw) {   // an odd roll (SODD) only exists for periodization with L % 4 == 0
         WL_CASE0(2); WL_CASE2(4); WL_CASE0(6); WL_CASE2(8); WL_CASE0(10); WL_CASE2Q(12); WL_CASE0L(14); WL_CASE2Q(16); WL_CASE0Q(18); WL_CASE2Q(20);
         default: return WL_ERR_UNSUPPORTED;
     }
 #undef WL_CASE0Q
 #undef WL_CASE0L
-#undef WL_ARGS_L
 #undef WL_CASE2Q
 #undef WL_CASE0
 #undef WL_CASE2
-#undef WL_ARGS
 }
 
 extern "C" int wl_dwt2d_synthesis_stream_ex(const void* ll, int64_t ll_plane_stride, int ll_row_stride, const void* highs,
@@ -437,16 +386,9 @@ extern "C" int wl_dwt2d_synthesis_stream_ex(const void* ll, int64_t ll_plane_str
     if (wl_streaming_off()) return WL_ERR_UNSUPPORTED;
     if (mode == 2 && (2 * Kh < L - 2 || 2 * Kw < L - 2)) return WL_ERR_UNSUPPORTED;   // single-fold corner: direct kernels
     if (planes == 0) return 0;
-    if (dtype == WL_F32)
-        return wl_sfb_strip_dispatch<float>(L, ll, ll_plane_stride, ll_row_stride, highs, y, planes, Kh, Kw, OH, OW,
-                                            g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, policy, stream, (float*)tap_scratch, tap_state);
-    if (dtype == WL_F16)
-        return wl_sfb_strip_dispatch<wl_half>(L, ll, ll_plane_stride, ll_row_stride, highs, y, planes, Kh, Kw, OH, OW,
-                                              g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, policy, stream, (float*)tap_scratch, tap_state);
-    if (dtype == WL_BF16)
-        return wl_sfb_strip_dispatch<wl_bf16>(L, ll, ll_plane_stride, ll_row_stride, highs, y, planes, Kh, Kw, OH, OW,
-                                              g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, policy, stream, (float*)tap_scratch, tap_state);
-    return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
+    const WlSfbReq r = {ll, ll_plane_stride, ll_row_stride, highs, y, planes, Kh, Kw, OH, OW,
+                        {g_w_lo, g_w_hi, g_h_lo, g_h_hi}, L, L, mode, policy, (float*)tap_scratch, tap_state, stream};
+    WL_DISPATCH_FLOAT(dtype, return wl_sfb_strip_dispatch<T>(r));
 }
 
 extern "C" int wl_dwt2d_synthesis_stream(const void* ll, int64_t ll_plane_stride, int ll_row_stride, const void* highs,
@@ -696,13 +638,8 @@ extern "C" int wl_dtcwt_fwd_level12(const void* x, void* highs1, void* ll2, void
     if (mode != 1) return WL_ERR_UNSUPPORTED;                   // symmetric (coldfilt / rowdfilt know nothing else)
     if (planes == 0) return 0;
     if (wl_streaming_off()) return WL_ERR_UNSUPPORTED;
-    if (dtype == WL_F32)
-        return wl_dtfwd12_any<float>(x, highs1, ll2, highs2, planes, H, W, h0o, L0, h1o, L1, h0a, h0b, h1a, h1b, LQ, policy, stream);
-    if (dtype == WL_F16)
-        return wl_dtfwd12_any<wl_half>(x, highs1, ll2, highs2, planes, H, W, h0o, L0, h1o, L1, h0a, h0b, h1a, h1b, LQ, policy, stream);
-    if (dtype == WL_BF16)
-        return wl_dtfwd12_any<wl_bf16>(x, highs1, ll2, highs2, planes, H, W, h0o, L0, h1o, L1, h0a, h0b, h1a, h1b, LQ, policy, stream);
-    return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
+    WL_DISPATCH_FLOAT(dtype, return wl_dtfwd12_any<T>(x, highs1, ll2, highs2, planes, H, W, h0o, L0, h1o, L1, h0a, h0b, h1a, h1b, LQ,
+                                                      policy, stream));
 }
 
 // ---- lean level-1 forward / ScatLayer forward on the stagers and level-1 lanes of the fused kernel (MODE 0 / 1) ----------
