@@ -5,6 +5,7 @@
 #include "../../include/wavelets_hip.h"
 #include "wl_common.h"
 #include "wl_api_common.h"
+#include "wl_dt_api.h"
 #include <string.h>
 #include "wl_dwt_kernels.h"
 #include "wl_dwt_tile.h"
@@ -499,32 +500,6 @@ struct WlDtTile<double> {
     static int inv2(WlDtInv2Args<double>&, void*) { return WL_ERR_UNSUPPORTED; }
 };
 
-// the streaming level-1 forward over column strips lives in the strip translation unit (wl_strip_api.inc)
-int wl_dtfwd1_strip(const WlDtFwd1Args<float>& f, void* stream);
-int wl_dtfwd1_strip(const WlDtFwd1Args<wl_half>& f, void* stream);
-int wl_dtfwd1_strip(const WlDtFwd1Args<wl_bf16>& f, void* stream);
-int wl_dtfwd1_strip(const WlDtFwd1Args<double>& f, void* stream);
-int wl_dtfwd1_lean(const WlDtFwd1Args<float>& f, void* stream);     // lean level-1 / ScatLayer strip kernels (wl_dtcwt_fused.h)
-int wl_dtfwd1_lean(const WlDtFwd1Args<wl_half>& f, void* stream);
-int wl_dtfwd1_lean(const WlDtFwd1Args<wl_bf16>& f, void* stream);
-int wl_dtfwd1_lean(const WlDtFwd1Args<double>& f, void* stream);
-int wl_dtrot_lean(const WlDtFwd1Args<float>& f, const void* h2, int L2, void* stream);   // ... with the band-pass diagonal (MODE 6)
-int wl_dtrot_lean(const WlDtFwd1Args<wl_half>& f, const void* h2, int L2, void* stream);
-int wl_dtrot_lean(const WlDtFwd1Args<wl_bf16>& f, const void* h2, int L2, void* stream);
-int wl_dtrot_lean(const WlDtFwd1Args<double>& f, const void* h2, int L2, void* stream);
-int wl_dtfwd2_lean(const WlDtFwd2Args<float>& g, void* stream);     // streaming level >= 2 forward (wl_dtcwt_fused.h MODE 4)
-int wl_dtfwd2_lean(const WlDtFwd2Args<wl_half>& g, void* stream);
-int wl_dtfwd2_lean(const WlDtFwd2Args<wl_bf16>& g, void* stream);
-int wl_dtfwd2_lean(const WlDtFwd2Args<double>& g, void* stream);
-int wl_dtinv2_strip(const WlDtInv2Args<float>& f, void* stream);    // streaming level >= 2 inverse (wl_dtcwt_fused.h)
-int wl_dtinv2_strip(const WlDtInv2Args<wl_half>& f, void* stream);
-int wl_dtinv2_strip(const WlDtInv2Args<wl_bf16>& f, void* stream);
-int wl_dtinv2_strip(const WlDtInv2Args<double>& f, void* stream);
-int wl_dtinv1_strip(const WlDtInv1Args<float>& f, void* stream);
-int wl_dtinv1_strip(const WlDtInv1Args<wl_half>& f, void* stream);
-int wl_dtinv1_strip(const WlDtInv1Args<wl_bf16>& f, void* stream);
-int wl_dtinv1_strip(const WlDtInv1Args<double>& f, void* stream);
-
 // small planes, several per workgroup (wl_dtcwt_small.h): even sizes up to 64 x 64, the tabulated level-1 pairs, no colour
 // combination, float32 / float16
 static unsigned wl_magic(unsigned d) { return d <= 1 ? 0u : (unsigned)((0x100000000ULL + d - 1) / d); }
@@ -563,22 +538,11 @@ static int wl_dtfwd1_small(const WlDtFwd1Args<T>& a, void* stream) {
     return WL_ERR_UNSUPPORTED;
 }
 
+// Level 1 forward / ScatLayer forward of the struct an entry built (wl_dtfwd1_args + its outputs): the streaming kernels of the strip
+// unit (wl_dt_api.h), the small-plane kernel, the tile kernels, the generic kernel - the first that takes the case.
 template <typename T>
-static int wl_dtfwd1_launch(const void* x, void* ll, void* highs, void* z, void* drdx, void* drdy, int64_t planes,
-                            int C, int H, int W, const void* h0, int L0, const void* h1, int L1, int ext,
-                            int combine, double magbias, void* stream, const int64_t* zaddr = nullptr) {
-    typedef typename WlAcc<T>::type A;
-    WlDtFwd1Args<T> a;
-    {   // the layer's own (N, 7, C, q) layout unless the caller places the entries (zaddr: batch stride, lowpass, magnitudes)
-        const int64_t q = (int64_t)((H + (H & 1)) / 2) * ((W + (W & 1)) / 2);
-        a.z_bs = zaddr ? zaddr[0] : 7 * C * q; a.z_ll_off = zaddr ? zaddr[1] : 0; a.z_mag_off = zaddr ? zaddr[2] : C * q;
-    }
-    a.x = (const T*)x; a.ll = (T*)ll; a.highs = (T*)highs; a.z = (T*)z; a.drdx = (T*)drdx; a.drdy = (T*)drdy;
-    a.h0 = (const A*)h0; a.h1 = (const A*)h1;
-    a.NC = planes; a.C = C; a.H = H; a.W = W; a.He = H + (H & 1); a.We = W + (W & 1);
-    a.L0 = L0; a.L1 = L1; a.M = (L0 > L1 ? L0 : L1) / 2; a.ext = ext;
-    a.combine = combine; a.magbias = (A)magbias;
-    const int64_t units = combine ? planes / 3 : planes;
+static int wl_dtfwd1_launch(WlDtFwd1Args<T>& a, void* stream) {
+    const int64_t units = a.combine ? a.NC / 3 : a.NC;
     if ((int64_t)a.He * a.We < (1LL << 30) && !wl_options().generic_only) {
         int rc = wl_options().no_stream ? WL_ERR_UNSUPPORTED : wl_dtfwd1_lean(a, stream);
         if (rc != WL_ERR_UNSUPPORTED) return rc;
@@ -604,8 +568,11 @@ extern "C" int wl_dtcwt_fwd_level1(const void* x, void* ll, void* highs, int dty
     if (L0 < 1 || L1 < 1 || L0 > WL_MAX_TAPS || L1 > WL_MAX_TAPS) return WL_ERR_TAPS;
     if (!(L0 & 1) || !(L1 & 1)) return WL_ERR_UNSUPPORTED;   // even-length level-1 filters change the output size
     if (planes == 0) return 0;
-    WL_DISPATCH_DTYPE(dtype, return wl_dtfwd1_launch<T>(x, ll, highs, nullptr, nullptr, nullptr, planes, 1, H, W, h0,
-                                                        L0, h1, L1, wl_dt_ext(mode), 0, 0.0, stream));
+    WL_DISPATCH_DTYPE(dtype, {
+        WlDtFwd1Args<T> a = wl_dtfwd1_args<T>(x, planes, 1, H, W, h0, L0, h1, L1, wl_dt_ext(mode));
+        a.ll = (T*)ll; a.highs = (T*)highs;
+        return wl_dtfwd1_launch(a, stream);
+    });
     return 0;
 }
 
@@ -617,8 +584,12 @@ extern "C" int wl_scat_fwd_level1(const void* x, void* z, void* drdx, void* drdy
     if (L0 < 1 || L1 < 1 || L0 > WL_MAX_TAPS || L1 > WL_MAX_TAPS) return WL_ERR_TAPS;
     if (!(L0 & 1) || !(L1 & 1)) return WL_ERR_UNSUPPORTED;
     if (N == 0) return 0;
-    WL_DISPATCH_DTYPE(dtype, return wl_dtfwd1_launch<T>(x, ll, nullptr, z, drdx, drdy, N * C, C, H, W, h0, L0, h1,
-                                                        L1, wl_dt_ext(mode), combine_colour, magbias, stream));
+    WL_DISPATCH_DTYPE(dtype, {
+        WlDtFwd1Args<T> a = wl_dtfwd1_args<T>(x, N * C, C, H, W, h0, L0, h1, L1, wl_dt_ext(mode));
+        a.ll = (T*)ll; a.z = (T*)z; a.drdx = (T*)drdx; a.drdy = (T*)drdy;
+        a.combine = combine_colour; a.magbias = (WlDtFwd1Args<T>::A)magbias;
+        return wl_dtfwd1_launch(a, stream);
+    });
     return 0;
 }
 
@@ -632,24 +603,13 @@ extern "C" int wl_scat_fwd_level1_into(const void* x, void* z, int64_t z_batch_s
     if (L0 < 1 || L1 < 1 || L0 > WL_MAX_TAPS || L1 > WL_MAX_TAPS) return WL_ERR_TAPS;
     if (!(L0 & 1) || !(L1 & 1)) return WL_ERR_UNSUPPORTED;
     if (N == 0) return 0;
-    const int64_t zaddr[3] = {z_batch_stride, z_ll_offset, z_mag_offset};
-    WL_DISPATCH_DTYPE(dtype, return wl_dtfwd1_launch<T>(x, ll, nullptr, z, nullptr, nullptr, N * C, C, H, W, h0, L0, h1,
-                                                        L1, wl_dt_ext(mode), 0, magbias, stream, zaddr));
+    WL_DISPATCH_DTYPE(dtype, {
+        WlDtFwd1Args<T> a = wl_dtfwd1_args<T>(x, N * C, C, H, W, h0, L0, h1, L1, wl_dt_ext(mode));
+        a.ll = (T*)ll; a.z = (T*)z; a.magbias = (WlDtFwd1Args<T>::A)magbias;
+        a.z_bs = z_batch_stride; a.z_ll_off = z_ll_offset; a.z_mag_off = z_mag_offset;   // the caller places the entries
+        return wl_dtfwd1_launch(a, stream);
+    });
     return 0;
-}
-
-template <typename T>
-static int wl_scat2_run(const void* x, void* z, int64_t z_bs, int64_t z_ll, int64_t z_mag, int64_t N, int C, int H, int W,
-                        const void* h0a, const void* h0b, const void* h1a, const void* h1b, int L, double magbias, void* stream) {
-    typedef typename WlAcc<T>::type A;
-    WlDtFwd2Args<T> a;
-    a.x = (const T*)x; a.ll = nullptr; a.highs = nullptr;
-    a.h0a = (const A*)h0a; a.h0b = (const A*)h0b; a.h1a = (const A*)h1a; a.h1b = (const A*)h1b;
-    a.NC = N * C; a.H = H; a.W = W; a.padr = a.padc = 0; a.He = H; a.We = W; a.L = L;
-    a.TH = a.TW = a.tiles_x = a.tiles_y = 0; a.nblocks = 0;
-    a.z = (T*)z; a.z_bs = z_bs; a.z_ll_off = z_ll; a.z_mag_off = z_mag; a.C = C; a.magbias = (A)magbias;
-    if (wl_options().no_stream || wl_options().generic_only) return WL_ERR_UNSUPPORTED;
-    return wl_dtfwd2_lean(a, stream);
 }
 
 extern "C" int wl_scat_fwd_level2_into(const void* x, void* z, int64_t z_batch_stride, int64_t z_ll_offset, int64_t z_mag_offset,
@@ -659,34 +619,26 @@ extern "C" int wl_scat_fwd_level2_into(const void* x, void* z, int64_t z_batch_s
     if (L < 2 || L > WL_MAX_TAPS || (L & 1)) return WL_ERR_TAPS;
     if ((H & 3) || (W & 3)) return WL_ERR_UNSUPPORTED;               // (ScatLayerj2 pads its input to a multiple of 8)
     if (N == 0) return 0;
-    WL_DISPATCH_DTYPE(dtype, return wl_scat2_run<T>(x, z, z_batch_stride, z_ll_offset, z_mag_offset, N, C, H, W, h0a, h0b, h1a, h1b,
-                                                    L, magbias, stream));
+    WL_DISPATCH_DTYPE(dtype, {                                       // (the streaming kernel or none)
+        WlDtFwd2Args<T> a = wl_dtfwd2_args<T>(x, N * C, H, W, h0a, h0b, h1a, h1b, L);
+        a.z = (T*)z; a.z_bs = z_batch_stride; a.z_ll_off = z_ll_offset; a.z_mag_off = z_mag_offset;
+        a.C = C; a.magbias = (WlDtFwd2Args<T>::A)magbias;
+        return wl_streaming_off() ? WL_ERR_UNSUPPORTED : wl_dtfwd2_lean(a, stream);
+    });
     return 0;
 }
 
 // ---- level 1 with the band-pass diagonal ('near_sym_b_bp'; wl_dtcwt_rot.h; reference dtcwt/transform_funcs.py:124-149,
 // scatternet/lowlevel.py:140-182) ----
 template <typename T>
-static int wl_dtfwd1_rot_run(const void* x, void* ll, void* re, void* im, int64_t N, int C, int H, int W, const void* h0, int L0,
-                             const void* h1, int L1, const void* h2, int L2, int ext, int scat, double magbias, void* stream) {
+static int wl_dtfwd1_rot_run(WlDtRotArgs<T>& a, int scat, void* stream) {
     typedef typename WlAcc<T>::type A;
-    WlDtRotArgs<T> a;
-    a.x = (const T*)x; a.ll = (T*)ll; a.re = (T*)re; a.im = (T*)im;
-    a.h0 = (const A*)h0; a.h1 = (const A*)h1; a.h2 = (const A*)h2;
-    a.planes = N * C; a.C = C; a.H = H; a.W = W; a.L0 = L0; a.L1 = L1; a.L2 = L2; a.ext = ext; a.bias = magbias;
-    if (scat && ext == WL_EXT_SYM && !wl_options().no_stream && !wl_options().generic_only && !(H & 1) && !(W & 1)) {
+    if (scat && a.ext == WL_EXT_SYM && !wl_streaming_off() && !(a.H & 1) && !(a.W & 1)) {
         // ScatLayer inference on wide planes that fill the chip: the lean streaming kernel with a third row filter and window
         // (wl_dtcwt_fused.h MODE 6) writes the same (N, 7, C, H/2, W/2) tensor
-        WlDtFwd1Args<T> f;
-        const int64_t q = (int64_t)(H / 2) * (W / 2);
-        f.z_bs = 7 * C * q; f.z_ll_off = 0; f.z_mag_off = C * q;
-        f.x = (const T*)x; f.ll = nullptr; f.highs = nullptr; f.z = (T*)re; f.drdx = f.drdy = nullptr;
-        f.h0 = (const A*)h0; f.h1 = (const A*)h1;
-        f.NC = N * C; f.C = C; f.H = H; f.W = W; f.He = H; f.We = W;
-        f.L0 = L0; f.L1 = L1; f.M = (L0 > L1 ? L0 : L1) / 2; f.ext = ext;
-        f.combine = 0; f.magbias = (A)magbias;
-        f.TH = f.TW = f.tiles_x = f.tiles_y = 0; f.nblocks = 0; f.run_len = f.runs_x = 0;
-        const int rc = wl_dtrot_lean(f, h2, L2, stream);
+        WlDtFwd1Args<T> f = wl_dtfwd1_args<T>(a.x, a.planes, a.C, a.H, a.W, a.h0, a.L0, a.h1, a.L1, a.ext);
+        f.z = a.re; f.magbias = (A)a.bias;
+        const int rc = wl_dtrot_lean(f, a.h2, a.L2, stream);
         if (rc != WL_ERR_UNSUPPORTED) return rc;
     }
     const int M = WlDtFwd1Rot<T, 0>::M;
@@ -699,7 +651,7 @@ static int wl_dtfwd1_rot_run(const void* x, void* ll, void* re, void* im, int64_
         if (a.lds_bytes <= 64 * 1024) break;
     }
     a.TH = TH;
-    a.tiles_x = wl_cdiv(W, 64); a.tiles_y = wl_cdiv(H, TH);
+    a.tiles_x = wl_cdiv(a.W, 64); a.tiles_y = wl_cdiv(a.H, TH);
     a.nblocks = a.planes * a.tiles_x * a.tiles_y;
     if (scat) return wl_launch<WlDtFwd1Rot<T, 1> >(a, a.nblocks, (size_t)a.lds_bytes, stream);
     return wl_launch<WlDtFwd1Rot<T, 0> >(a, a.nblocks, (size_t)a.lds_bytes, stream);
@@ -716,23 +668,16 @@ extern "C" int wl_dtcwt_fwd_level1_rot(const void* x, void* ll, void* re, void* 
     if ((H & 1) || (W & 1)) return WL_ERR_UNSUPPORTED;                     // q2c pairs rows and columns (the modules pad first)
     if ((int64_t)H * W >= (1LL << 30)) return WL_ERR_UNSUPPORTED;
     if (N == 0) return 0;
-    WL_DISPATCH_DTYPE(dtype, return wl_dtfwd1_rot_run<T>(x, ll, re, im, N, C, H, W, h0, L0, h1, L1, h2, L2, wl_dt_ext(mode), scat, magbias, stream));
+    WL_DISPATCH_DTYPE(dtype, {
+        WlDtRotArgs<T> a = wl_dtrot_args<T>(x, ll, re, im, N * C, C, H, W, h0, L0, h1, L1, h2, L2, wl_dt_ext(mode), magbias);
+        return wl_dtfwd1_rot_run(a, scat, stream);
+    });
     return 0;
 }
 
 template <typename T>
-static int wl_dtfwd2_launch(const void* x, void* ll, void* highs, int64_t planes, int H, int W, const void* h0a,
-                            const void* h0b, const void* h1a, const void* h1b, int L, void* stream) {
-    typedef typename WlAcc<T>::type A;
-    WlDtFwd2Args<T> a;
-    a.x = (const T*)x; a.ll = (T*)ll; a.highs = (T*)highs;
-    a.h0a = (const A*)h0a; a.h0b = (const A*)h0b; a.h1a = (const A*)h1a; a.h1b = (const A*)h1b;
-    a.NC = planes; a.H = H; a.W = W;
-    a.z = nullptr; a.z_bs = a.z_ll_off = a.z_mag_off = 0; a.C = 1; a.magbias = (A)0;
-    a.padr = (H % 4) ? 1 : 0; a.padc = (W % 4) ? 1 : 0;
-    a.He = H + 2 * a.padr; a.We = W + 2 * a.padc;
-    a.L = L;
-    if ((int64_t)H * W < (1LL << 30) && !wl_options().generic_only) {
+static int wl_dtfwd2_launch(WlDtFwd2Args<T>& a, void* stream) {
+    if ((int64_t)a.H * a.W < (1LL << 30) && !wl_options().generic_only) {
         int rc = wl_options().no_stream ? WL_ERR_UNSUPPORTED : wl_dtfwd2_lean(a, stream);
         if (rc != WL_ERR_UNSUPPORTED) return rc;
         rc = WlDtTile<T>::fwd2(a, stream);
@@ -742,7 +687,7 @@ static int wl_dtfwd2_launch(const void* x, void* ll, void* highs, int64_t planes
     while (wl_dtfwd2_lds(a) > 60 * 1024 && a.TW > 8) a.TW /= 2;
     while (wl_dtfwd2_lds(a) > 60 * 1024 && a.TH > 4) a.TH /= 2;
     a.tiles_x = wl_cdiv(a.We / 2, a.TW); a.tiles_y = wl_cdiv(a.He / 2, a.TH);
-    return wl_launch<WlDtFwd2<T> >(a, planes * a.tiles_x * a.tiles_y, wl_dtfwd2_lds(a), stream);
+    return wl_launch<WlDtFwd2<T> >(a, a.NC * a.tiles_x * a.tiles_y, wl_dtfwd2_lds(a), stream);
 }
 
 extern "C" int wl_dtcwt_fwd_level2(const void* x, void* ll, void* highs, int dtype, int64_t planes, int H, int W,
@@ -751,21 +696,17 @@ extern "C" int wl_dtcwt_fwd_level2(const void* x, void* ll, void* highs, int dty
     if (planes < 0 || H < 2 || W < 2 || (H & 1) || (W & 1)) return WL_ERR_SHAPE;
     if (L < 2 || L > WL_MAX_TAPS || (L & 1)) return WL_ERR_TAPS;
     if (planes == 0) return 0;
-    WL_DISPATCH_DTYPE(dtype, return wl_dtfwd2_launch<T>(x, ll, highs, planes, H, W, h0a, h0b, h1a, h1b, L, stream));
+    WL_DISPATCH_DTYPE(dtype, {
+        WlDtFwd2Args<T> a = wl_dtfwd2_args<T>(x, planes, H, W, h0a, h0b, h1a, h1b, L);
+        a.ll = (T*)ll; a.highs = (T*)highs;
+        return wl_dtfwd2_launch(a, stream);
+    });
     return 0;
 }
 
 template <typename T>
-static int wl_dtinv1_launch(const void* ll, int64_t ll_ps, int ll_rs, const void* highs, void* y, int64_t planes,
-                            int H, int W, const void* g0, int L0, const void* g1, int L1, int ext, void* stream) {
-    typedef typename WlAcc<T>::type A;
-    WlDtInv1Args<T> a;
-    a.ll = (const T*)ll; a.highs = (const T*)highs; a.y = (T*)y;
-    a.g0 = (const A*)g0; a.g1 = (const A*)g1;
-    a.NC = planes; a.ll_plane_stride = ll_ps; a.ll_row_stride = ll_rs;
-    a.H = H; a.W = W; a.L0 = L0; a.L1 = L1; a.M = (L0 > L1 ? L0 : L1) / 2; a.ext = ext;
-    a.sz = a.sdx = a.sdy = nullptr; a.C = 1; a.combine = 0;
-    if ((int64_t)H * W < (1LL << 30) && ll_ps < (1LL << 30) && (int64_t)H * ll_rs < (1LL << 30) &&
+static int wl_dtinv1_launch(WlDtInv1Args<T>& a, void* stream) {
+    if ((int64_t)a.H * a.W < (1LL << 30) && a.ll_plane_stride < (1LL << 30) && (int64_t)a.H * a.ll_row_stride < (1LL << 30) &&
         !wl_options().generic_only) {
         int rc = wl_options().no_stream ? WL_ERR_UNSUPPORTED : wl_dtinv1_strip(a, stream);
         if (rc != WL_ERR_UNSUPPORTED) return rc;
@@ -775,8 +716,8 @@ static int wl_dtinv1_launch(const void* ll, int64_t ll_ps, int ll_rs, const void
     a.TH = 16; a.TW = 64;
     while (wl_dtinv1_lds(a) > 60 * 1024 && a.TW > 16) a.TW /= 2;
     while (wl_dtinv1_lds(a) > 60 * 1024 && a.TH > 4) a.TH /= 2;
-    a.tiles_x = wl_cdiv(W, a.TW); a.tiles_y = wl_cdiv(H, a.TH);
-    return wl_launch<WlDtInv1<T> >(a, planes * a.tiles_x * a.tiles_y, wl_dtinv1_lds(a), stream);
+    a.tiles_x = wl_cdiv(a.W, a.TW); a.tiles_y = wl_cdiv(a.H, a.TH);
+    return wl_launch<WlDtInv1<T> >(a, a.NC * a.tiles_x * a.tiles_y, wl_dtinv1_lds(a), stream);
 }
 
 extern "C" int wl_dtcwt_inv_level1(const void* ll, int64_t ll_plane_stride, int ll_row_stride, const void* highs,
@@ -789,23 +730,17 @@ extern "C" int wl_dtcwt_inv_level1(const void* ll, int64_t ll_plane_stride, int 
     if (planes == 0) return 0;
     // the reference ignores `mode` (always symmetric) when there are no highpass inputs (transform_funcs.py:158-159)
     const int ext = highs ? wl_dt_ext(mode) : WL_EXT_SYM;
-    WL_DISPATCH_DTYPE(dtype, return wl_dtinv1_launch<T>(ll, ll_plane_stride, ll_row_stride, highs, y, planes, H, W, g0,
-                                                        L0, g1, L1, ext, stream));
+    WL_DISPATCH_DTYPE(dtype, {
+        WlDtInv1Args<T> a = wl_dtinv1_args<T>(y, planes, 1, H, W, g0, L0, g1, L1, ext);
+        a.ll = (const T*)ll; a.highs = (const T*)highs; a.ll_plane_stride = ll_plane_stride; a.ll_row_stride = ll_row_stride;
+        return wl_dtinv1_launch(a, stream);
+    });
     return 0;
 }
 
 template <typename T>
-static int wl_scat_bwd_launch(const void* dz, const void* drdx, const void* drdy, void* dx, int64_t N, int C, int H, int W,
-                              const void* h0, int L0, const void* h1, int L1, int ext, int combine, void* stream) {
-    typedef typename WlAcc<T>::type A;
-    WlDtInv1Args<T> a;
-    a.ll = nullptr; a.highs = nullptr; a.y = (T*)dx;
-    a.g0 = (const A*)h0; a.g1 = (const A*)h1;
-    a.NC = N * C; a.ll_plane_stride = 0; a.ll_row_stride = 0;
-    a.H = H; a.W = W; a.L0 = L0; a.L1 = L1; a.M = (L0 > L1 ? L0 : L1) / 2; a.ext = ext;
-    a.sz = (const T*)dz; a.sdx = (const T*)drdx; a.sdy = (const T*)drdy; a.C = C; a.combine = combine;
-    if ((int64_t)H * W >= (1LL << 30)) return WL_ERR_UNSUPPORTED;
-    a.TH = a.TW = a.tiles_x = a.tiles_y = 0; a.nblocks = 0;
+static int wl_scat_bwd_launch(WlDtInv1Args<T>& a, void* stream) {
+    if ((int64_t)a.H * a.W >= (1LL << 30)) return WL_ERR_UNSUPPORTED;
     // wide planes that fill the chip: the streaming level-1 inverse with the scattering prologue in its stagers
     const int rc = wl_options().no_stream ? WL_ERR_UNSUPPORTED : wl_dtinv1_strip(a, stream);
     if (rc != WL_ERR_UNSUPPORTED) return rc;
@@ -824,22 +759,17 @@ extern "C" int wl_scat_bwd_level1(const void* dz, const void* drdx, const void* 
     if (L0 < 1 || L1 < 1 || L0 > WL_MAX_TAPS || L1 > WL_MAX_TAPS) return WL_ERR_TAPS;
     if (wl_options().generic_only) return WL_ERR_UNSUPPORTED;
     if (N == 0) return 0;
-    WL_DISPATCH_DTYPE(dtype, return wl_scat_bwd_launch<T>(dz, drdx, drdy, dx, N, C, H, W, h0, L0, h1, L1, wl_dt_ext(mode),
-                                                          combine_colour, stream));
+    WL_DISPATCH_DTYPE(dtype, {
+        WlDtInv1Args<T> a = wl_dtinv1_args<T>(dx, N * C, C, H, W, h0, L0, h1, L1, wl_dt_ext(mode));
+        a.sz = (const T*)dz; a.sdx = (const T*)drdx; a.sdy = (const T*)drdy; a.combine = combine_colour;
+        return wl_scat_bwd_launch(a, stream);
+    });
     return 0;
 }
 
 template <typename T>
-static int wl_dtinv2_launch(const void* ll, int64_t ll_ps, int ll_rs, const void* highs, void* y, int64_t planes,
-                            int h, int w, const void* g0a, const void* g0b, const void* g1a, const void* g1b, int L,
-                            void* stream) {
-    typedef typename WlAcc<T>::type A;
-    WlDtInv2Args<T> a;
-    a.ll = (const T*)ll; a.highs = (const T*)highs; a.y = (T*)y;
-    a.g0a = (const A*)g0a; a.g0b = (const A*)g0b; a.g1a = (const A*)g1a; a.g1b = (const A*)g1b;
-    a.NC = planes; a.ll_plane_stride = ll_ps; a.ll_row_stride = ll_rs;
-    a.h = h; a.w = w; a.L = L;
-    if ((int64_t)h * w < (1LL << 28) && ll_ps < (1LL << 30) && (int64_t)h * ll_rs < (1LL << 30) &&
+static int wl_dtinv2_launch(WlDtInv2Args<T>& a, void* stream) {
+    if ((int64_t)a.h * a.w < (1LL << 28) && a.ll_plane_stride < (1LL << 30) && (int64_t)a.h * a.ll_row_stride < (1LL << 30) &&
         !wl_options().generic_only) {
         int rc = wl_options().no_stream ? WL_ERR_UNSUPPORTED : wl_dtinv2_strip(a, stream);
         if (rc != WL_ERR_UNSUPPORTED) return rc;
@@ -848,8 +778,8 @@ static int wl_dtinv2_launch(const void* ll, int64_t ll_ps, int ll_rs, const void
     }
     a.TH = 16; a.TW = 64;
     while (wl_dtinv2_lds(a) > 60 * 1024 && a.TW > 16) a.TW /= 2;
-    a.tiles_x = wl_cdiv(2 * w, a.TW); a.tiles_y = wl_cdiv(2 * h, a.TH);
-    return wl_launch<WlDtInv2<T> >(a, planes * a.tiles_x * a.tiles_y, wl_dtinv2_lds(a), stream);
+    a.tiles_x = wl_cdiv(2 * a.w, a.TW); a.tiles_y = wl_cdiv(2 * a.h, a.TH);
+    return wl_launch<WlDtInv2<T> >(a, a.NC * a.tiles_x * a.tiles_y, wl_dtinv2_lds(a), stream);
 }
 
 extern "C" int wl_dtcwt_inv_level2(const void* ll, int64_t ll_plane_stride, int ll_row_stride, const void* highs,
@@ -859,8 +789,10 @@ extern "C" int wl_dtcwt_inv_level2(const void* ll, int64_t ll_plane_stride, int 
     if (!ll && !highs) return WL_ERR_SHAPE;
     if (L < 2 || L > WL_MAX_TAPS || (L & 1)) return WL_ERR_TAPS;
     if (planes == 0) return 0;
-    WL_DISPATCH_DTYPE(dtype, return wl_dtinv2_launch<T>(ll, ll_plane_stride, ll_row_stride, highs, y, planes, h, w, g0a,
-                                                        g0b, g1a, g1b, L, stream));
+    WL_DISPATCH_DTYPE(dtype, {
+        WlDtInv2Args<T> a = wl_dtinv2_args<T>(ll, ll_plane_stride, ll_row_stride, highs, y, planes, h, w, g0a, g0b, g1a, g1b, L);
+        return wl_dtinv2_launch(a, stream);
+    });
     return 0;
 }
 

@@ -71,13 +71,13 @@ struct WlSfbPyrReq {
 
 // ---- dtype dispatch --------------------------------------------------------------------------------
 // A statement with T = the element type of `dtype`: every dtype of the ABI ...
-#define WL_DISPATCH_DTYPE(dtype, CALL)            \
-    switch (dtype) {                              \
-        case WL_F32: { typedef float T; CALL; } break;   \
-        case WL_F16: { typedef wl_half T; CALL; } break; \
-        case WL_BF16: { typedef wl_bf16 T; CALL; } break; \
-        case WL_F64: { typedef double T; CALL; } break;  \
-        default: return WL_ERR_DTYPE;             \
+#define WL_DISPATCH_DTYPE(dtype, ...)                      \
+    switch (dtype) {                                       \
+        case WL_F32: { typedef float T; __VA_ARGS__; } break;    \
+        case WL_F16: { typedef wl_half T; __VA_ARGS__; } break;  \
+        case WL_BF16: { typedef wl_bf16 T; __VA_ARGS__; } break; \
+        case WL_F64: { typedef double T; __VA_ARGS__; } break;   \
+        default: return WL_ERR_DTYPE;                      \
     }
 // ... or, for the kernels without a float64 form, a statement that returns: float64 is valid but not this kernel's
 // (WL_ERR_UNSUPPORTED), anything else is no dtype

@@ -68,6 +68,16 @@ struct WlDtFusedArgs {
     int lds_bytes;
     const float* h2; int L2;       // MODE 6: the band-pass filter of the diagonal sub-band ('near_sym_b_bp'), L2 <= 2 M + 1 taps
 };
+// Host: the one place the struct is built - level 1 as the caller made it (wl_dtfwd1_args), the level-2 outputs and filters where the
+// launch has a level 2, everything else zero: the launchers add the strip geometry, the MODE 6 launch its h2 / L2.
+template <typename T>
+inline WlDtFusedArgs<T> wl_dtfused_args(const WlDtFwd1Args<T>& f, T* ll2 = nullptr, T* highs2 = nullptr, const void* h0a = nullptr,
+                                        const void* h0b = nullptr, const void* h1a = nullptr, const void* h1b = nullptr) {
+    WlDtFusedArgs<T> a = {};
+    a.f = f; a.ll2 = ll2; a.highs2 = highs2;
+    a.h0a = (const float*)h0a; a.h0b = (const float*)h0b; a.h1a = (const float*)h1a; a.h1b = (const float*)h1b;
+    return a;
+}
 
 // MODE 2: levels 1 + 2 (above).  The same stagers and level-1 lanes without the level-2 waves are the lean level-1 kernels:
 // MODE 0: fwd_j1 alone (lowpass and band-pass coefficients to memory), MODE 1: ScatLayerj1_f.forward (scatternet/lowlevel.py:

@@ -49,6 +49,19 @@ struct WlDtInv21Args {
     int l1_off, l1_pitch;          // LL1 ring: 4 * NG rows of float32
     int lds_bytes;
 };
+// Host: the one place the struct is built (everything else zero; wl_dtinv21_launch adds the strip and segment geometry).
+template <typename T>
+inline WlDtInv21Args<T> wl_dtinv21_args(const void* ll2, int64_t ll2_ps, int ll2_rs, const void* highs2, const void* highs1, void* y,
+                                        int64_t NC, int H, int W, const void* g0o, const void* g1o, const void* g0a,
+                                        const void* g0b, const void* g1a, const void* g1b) {
+    typedef typename WlAcc<T>::type A;
+    WlDtInv21Args<T> a = {};
+    a.ll2 = (const T*)ll2; a.highs2 = (const T*)highs2; a.highs1 = (const T*)highs1; a.y = (T*)y;
+    a.g0o = (const A*)g0o; a.g1o = (const A*)g1o;
+    a.g0a = (const A*)g0a; a.g0b = (const A*)g0b; a.g1a = (const A*)g1a; a.g1b = (const A*)g1b;
+    a.NC = NC; a.ll2_ps = ll2_ps; a.ll2_rs = ll2_rs; a.H = H; a.W = W;
+    return a;
+}
 
 template <typename T, int L0, int L1, int LQ>
 struct WlDtInv21Strip {

@@ -66,6 +66,21 @@ struct WlDtFwd1Args {
     // small-plane kernel (wl_dtcwt_small.h): ceil(2^32 / d) (0 for d = 1) for d = (H + 2M)(W + 2M), W + 2M, W, (H/2)(W/2), W/2
     unsigned mg_q, mg_w, mg_w2, nblocks_q, mg_qc;
 };
+// Host: the one place each argument struct of this file is built.  Every field starts at zero; set here is what every launch sets
+// the same way (the input, the taps, the sizes and what follows from them, the layer's own (N, 7, C, q) layout of z); a caller
+// then assigns only what is its own - outputs, the scattering extras, a placed z - and the launcher that runs a kernel its geometry.
+template <typename T>
+inline WlDtFwd1Args<T> wl_dtfwd1_args(const void* x, int64_t NC, int C, int H, int W, const void* h0, int L0, const void* h1,
+                                      int L1, int ext) {
+    typedef typename WlAcc<T>::type A;
+    WlDtFwd1Args<T> a = {};
+    a.x = (const T*)x; a.h0 = (const A*)h0; a.h1 = (const A*)h1;
+    a.NC = NC; a.C = C; a.H = H; a.W = W; a.He = H + (H & 1); a.We = W + (W & 1);
+    a.L0 = L0; a.L1 = L1; a.M = (L0 > L1 ? L0 : L1) / 2; a.ext = ext;
+    const int64_t q = (int64_t)(a.He / 2) * (a.We / 2);
+    a.z_bs = 7 * C * q; a.z_ll_off = 0; a.z_mag_off = C * q;
+    return a;
+}
 
 template <typename T>
 WL_HD size_t wl_dtfwd1_lds(const WlDtFwd1Args<T>& a) {
@@ -262,6 +277,19 @@ struct WlDtFwd2Args {
     int C;
     A magbias;
 };
+template <typename T>
+inline WlDtFwd2Args<T> wl_dtfwd2_args(const void* x, int64_t NC, int H, int W, const void* h0a, const void* h0b, const void* h1a,
+                                      const void* h1b, int L) {
+    typedef typename WlAcc<T>::type A;
+    WlDtFwd2Args<T> a = {};
+    a.x = (const T*)x;
+    a.h0a = (const A*)h0a; a.h0b = (const A*)h0b; a.h1a = (const A*)h1a; a.h1b = (const A*)h1b;
+    a.NC = NC; a.C = 1; a.H = H; a.W = W;
+    a.padr = (H % 4) ? 1 : 0; a.padc = (W % 4) ? 1 : 0;
+    a.He = H + 2 * a.padr; a.We = W + 2 * a.padc;
+    a.L = L;
+    return a;
+}
 
 template <typename T>
 WL_HD size_t wl_dtfwd2_lds(const WlDtFwd2Args<T>& a) {
@@ -394,6 +422,16 @@ struct WlDtInv1Args {
     const T* sz; const T* sdx; const T* sdy;
     int C, combine;
 };
+template <typename T>
+inline WlDtInv1Args<T> wl_dtinv1_args(void* y, int64_t NC, int C, int H, int W, const void* g0, int L0, const void* g1, int L1,
+                                      int ext) {
+    typedef typename WlAcc<T>::type A;
+    WlDtInv1Args<T> a = {};
+    a.y = (T*)y; a.g0 = (const A*)g0; a.g1 = (const A*)g1;
+    a.NC = NC; a.C = C; a.H = H; a.W = W;
+    a.L0 = L0; a.L1 = L1; a.M = (L0 > L1 ? L0 : L1) / 2; a.ext = ext;
+    return a;
+}
 
 template <typename T>
 WL_HD size_t wl_dtinv1_lds(const WlDtInv1Args<T>& a) {
@@ -495,6 +533,17 @@ struct WlDtInv2Args {
     int TH, TW, tiles_x, tiles_y;   // output tile, multiples of 4
     int64_t nblocks;                // specialised kernel: grid size for the XCD-aware block remap (0 = off)
 };
+template <typename T>
+inline WlDtInv2Args<T> wl_dtinv2_args(const void* ll, int64_t ll_ps, int ll_rs, const void* highs, void* y, int64_t NC, int h,
+                                      int w, const void* g0a, const void* g0b, const void* g1a, const void* g1b, int L) {
+    typedef typename WlAcc<T>::type A;
+    WlDtInv2Args<T> a = {};
+    a.ll = (const T*)ll; a.highs = (const T*)highs; a.y = (T*)y;
+    a.g0a = (const A*)g0a; a.g0b = (const A*)g0b; a.g1a = (const A*)g1a; a.g1b = (const A*)g1b;
+    a.NC = NC; a.ll_plane_stride = ll_ps; a.ll_row_stride = ll_rs;
+    a.h = h; a.w = w; a.L = L;
+    return a;
+}
 
 template <typename T>
 WL_HD size_t wl_dtinv2_lds(const WlDtInv2Args<T>& a) {

@@ -29,6 +29,17 @@ struct WlDtRotArgs {
     int in_pitch, mid_off, lds_bytes;
     double bias;
 };
+// Host: the one place the struct is built (everything else zero; wl_dtfwd1_rot_run adds the tile geometry).
+template <typename T>
+inline WlDtRotArgs<T> wl_dtrot_args(const void* x, void* ll, void* re, void* im, int64_t planes, int C, int H, int W,
+                                    const void* h0, int L0, const void* h1, int L1, const void* h2, int L2, int ext, double bias) {
+    typedef typename WlAcc<T>::type A;
+    WlDtRotArgs<T> a = {};
+    a.x = (const T*)x; a.ll = (T*)ll; a.re = (T*)re; a.im = (T*)im;
+    a.h0 = (const A*)h0; a.h1 = (const A*)h1; a.h2 = (const A*)h2;
+    a.planes = planes; a.C = C; a.H = H; a.W = W; a.L0 = L0; a.L1 = L1; a.L2 = L2; a.ext = ext; a.bias = bias;
+    return a;
+}
 
 template <typename T, int SCAT>
 struct WlDtFwd1Rot {

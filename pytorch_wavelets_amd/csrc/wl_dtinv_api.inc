@@ -1,7 +1,7 @@
 // C ABI of the fused DTCWT inverse (levels 2 + 1 in one streaming launch, wl_dtcwt_inv_fused.h).  Its own translation unit in
 // the HIP build (wl_dtinv_hip.hip, -fno-slp-vectorize like the other streaming kernels); included after the backend header.
 #include "wl_api_common.h"
-int wl_streaming_off();   // wl_api.inc: 1 when the streaming kernels are switched off (generic_only / no_stream)
+#include "wl_dt_api.h"      // wl_streaming_off
 #include "wl_dtcwt_inv_fused.h"
 
 template <typename T, int L0, int L1, int LQ>
@@ -80,20 +80,14 @@ static int wl_dtinv21_launch(WlDtInv21Args<T>& a, void* stream) {
 }
 
 template <typename T>
-static int wl_dtinv21_any(const void* ll2, int64_t ll2_ps, int ll2_rs, const void* highs2, const void* highs1, void* y,
-                          int64_t planes, int H, int W, const void* g0o, int L0, const void* g1o, int L1, const void* g0a,
-                          const void* g0b, const void* g1a, const void* g1b, int LQ, int policy, void* stream) {
-    typedef typename WlAcc<T>::type A;
+static int wl_dtinv21_any(WlDtInv21Args<T>& a, int L0, int L1, int LQ, int policy, void* stream) {
     const int SZ = (int)sizeof(T);
-    WlDtInv21Args<T> a;
-    a.ll2 = (const T*)ll2; a.highs2 = (const T*)highs2; a.highs1 = (const T*)highs1; a.y = (T*)y;
-    a.g0o = (const A*)g0o; a.g1o = (const A*)g1o;
-    a.g0a = (const A*)g0a; a.g0b = (const A*)g0b; a.g1a = (const A*)g1a; a.g1b = (const A*)g1b;
-    a.NC = planes; a.ll2_ps = ll2_ps; a.ll2_rs = ll2_rs; a.H = H; a.W = W;
+    const int64_t planes = a.NC;
+    const int H = a.H, W = a.W;
     if ((H % 4) || (W % 4) || H < 32 || W < 32 || (int64_t)H * W >= (1LL << 28)) return WL_ERR_UNSUPPORTED;
     // 8-byte loads of ll2 pixel pairs and (re, im) pairs, 8-byte stores of y
-    if ((uintptr_t)ll2 % (2 * SZ) || (uintptr_t)highs2 % (2 * SZ) || (uintptr_t)highs1 % (2 * SZ) || (uintptr_t)y % (2 * SZ) ||
-        (ll2_rs & 1) || (ll2_ps & 1)) return WL_ERR_UNSUPPORTED;
+    if ((uintptr_t)a.ll2 % (2 * SZ) || (uintptr_t)a.highs2 % (2 * SZ) || (uintptr_t)a.highs1 % (2 * SZ) || (uintptr_t)a.y % (2 * SZ) ||
+        (a.ll2_rs & 1) || (a.ll2_ps & 1)) return WL_ERR_UNSUPPORTED;
     // small work: per-level kernels (224-column planes only in numbers: 256x3x224^2 J = 2 inverse 0.246 -> 0.227 ms, 128x3x224^2 0.117 -> 0.129)
     if (!policy && (planes * (int64_t)wl_cdiv(H, 64) < wl_num_cus() || (W < 256 && !(W >= 224 && planes >= 3 * (int64_t)wl_num_cus())))) return WL_ERR_UNSUPPORTED;
     if (LQ != 10) return WL_ERR_UNSUPPORTED;                                                       // qshift_a, qshift_06
@@ -113,6 +107,9 @@ extern "C" int wl_dtcwt_inv_level21(const void* ll2, int64_t ll2_plane_stride, i
     if (mode != 1) return WL_ERR_UNSUPPORTED;                   // symmetric (level 1 of the other modes pads with zeros: per-level kernels)
     if (planes == 0) return 0;
     if (wl_streaming_off()) return WL_ERR_UNSUPPORTED;
-    WL_DISPATCH_FLOAT(dtype, return wl_dtinv21_any<T>(ll2, ll2_plane_stride, ll2_row_stride, highs2, highs1, y, planes, H, W, g0o, L0,
-                                                      g1o, L1, g0a, g0b, g1a, g1b, LQ, policy, stream));
+    WL_DISPATCH_FLOAT(dtype, {
+        WlDtInv21Args<T> a = wl_dtinv21_args<T>(ll2, ll2_plane_stride, ll2_row_stride, highs2, highs1, y, planes, H, W, g0o, g1o,
+                                                g0a, g0b, g1a, g1b);
+        return wl_dtinv21_any(a, L0, L1, LQ, policy, stream);
+    });
 }

@@ -1,8 +1,8 @@
 // C ABI of the one-level streaming analysis over column strips (wl_dwt_strip.h).  Its own translation unit in the HIP
 // build (wl_strip_hip.hip, -fno-slp-vectorize like the other streaming kernels); included after the backend header.
 #include "wl_api_common.h"
+#include "wl_dt_api.h"      // wl_streaming_off, the launchers of part 4 that wl_api.inc calls
 #include "wl_dwt_strip.h"
-int wl_streaming_off();   // wl_api.inc: 1 when the streaming kernels are switched off (generic_only / no_stream)
 
 // planes of WL_FOUR_MIN .. 128 columns go four to a workgroup of the lean DTCWT / ScatLayer kernels (forward and inverse)
 #ifndef WL_FOUR_MIN
@@ -405,11 +405,18 @@ extern "C" int wl_dwt2d_synthesis_stream(const void* ll, int64_t ll_plane_stride
 // ---- streaming level-1 DTCWT forward / ScatLayer over column strips (wl_dtcwt_strip.h) ------------------------------
 #include "wl_dtcwt_strip.h"
 
+// The launchers of this part that wl_api.inc calls are declared in wl_dt_api.h and defined here once, as templates over the element
+// type: this instantiates one of them for the three types with streaming kernels (float64 is declined in the header).
+#define WL_DT_INSTANTIATE(NAME, ARGS, ...)                             \
+    template int NAME<float>(const ARGS<float>&, __VA_ARGS__);         \
+    template int NAME<wl_half>(const ARGS<wl_half>&, __VA_ARGS__);     \
+    template int NAME<wl_bf16>(const ARGS<wl_bf16>&, __VA_ARGS__);
+
 template <typename T, int L0, int L1>
 static int wl_dtfwd1_strip_launch(const WlDtFwd1Args<T>& f, void* stream) {
     typedef WlDtFwd1Strip<T, L0, L1> K;
     const int A = K::A, M = K::M;
-    WlDtStripArgs<T> a;
+    WlDtStripArgs<T> a = {};
     a.f = f;
     const int quads = f.We / 2;
     int cap = 64 * WL_STRIP_CWAVES;
@@ -459,7 +466,7 @@ static int wl_dtfwd1_strip_launch(const WlDtFwd1Args<T>& f, void* stream) {
 
 // Called by wl_dtfwd1_launch (wl_api.inc) before the tile kernels; WL_ERR_UNSUPPORTED = not this kernel's case.
 template <typename T>
-static int wl_dtfwd1_strip_any(const WlDtFwd1Args<T>& f, void* stream) {
+int wl_dtfwd1_strip(const WlDtFwd1Args<T>& f, void* stream) {
     const int SZ = (int)sizeof(T);
     if (f.combine || (f.ext != WL_EXT_SYM && f.ext != WL_EXT_ZERO)) return WL_ERR_UNSUPPORTED;
     if ((f.W * SZ) % 16 || (uintptr_t)f.x % 16 || f.W < 32 || f.H < 8 || (int64_t)f.He * f.We >= (1LL << 28)) return WL_ERR_UNSUPPORTED;
@@ -474,17 +481,14 @@ static int wl_dtfwd1_strip_any(const WlDtFwd1Args<T>& f, void* stream) {
     if (f.L0 == 5 && f.L1 == 3) return wl_dtfwd1_strip_launch<T, 5, 3>(f, stream);       // legall
     return WL_ERR_UNSUPPORTED;
 }
-int wl_dtfwd1_strip(const WlDtFwd1Args<float>& f, void* stream) { return wl_dtfwd1_strip_any<float>(f, stream); }
-int wl_dtfwd1_strip(const WlDtFwd1Args<wl_half>& f, void* stream) { return wl_dtfwd1_strip_any<wl_half>(f, stream); }
-int wl_dtfwd1_strip(const WlDtFwd1Args<wl_bf16>& f, void* stream) { return wl_dtfwd1_strip_any<wl_bf16>(f, stream); }
-int wl_dtfwd1_strip(const WlDtFwd1Args<double>&, void*) { return WL_ERR_UNSUPPORTED; }
+WL_DT_INSTANTIATE(wl_dtfwd1_strip, WlDtFwd1Args, void*)
 
 // ---- streaming level-1 DTCWT inverse over column strips ---------------------------------------------------------------
 template <typename T, int L0, int L1, int SCAT = 0, int PP = 1>
 static int wl_dtinv1_strip_launch1(const WlDtInv1Args<T>& f, void* stream) {
     typedef WlDtInv1Strip<T, L0, L1, SCAT, PP> K;
     const int M = K::M;
-    WlDtIStripArgs<T> a;
+    WlDtIStripArgs<T> a = {};
     a.f = f;
     const int W2 = f.W / 2;
     // one quad per stager lane: at most 256 quads (a strip's own and its neighbours' halo quads) are staged per quad row
@@ -523,7 +527,7 @@ static int wl_dtinv1_strip_launch(const WlDtInv1Args<T>& f, void* stream) {
 }
 
 template <typename T>
-static int wl_dtinv1_strip_any(const WlDtInv1Args<T>& f, void* stream) {
+int wl_dtinv1_strip(const WlDtInv1Args<T>& f, void* stream) {
     const int SZ = (int)sizeof(T);
     if (f.ext != WL_EXT_SYM && f.ext != WL_EXT_ZERO) return WL_ERR_UNSUPPORTED;
     if ((f.W & 1) || (f.H & 1) || f.W < 32 || f.H < 4 * f.M + 4 || (int64_t)f.H * f.W >= (1LL << 28) || (uintptr_t)f.y % (2 * SZ)) return WL_ERR_UNSUPPORTED;
@@ -550,10 +554,7 @@ static int wl_dtinv1_strip_any(const WlDtInv1Args<T>& f, void* stream) {
     if (f.L0 == 13 && f.L1 == 19) return wl_dtinv1_strip_launch<T, 13, 19>(f, stream);    // near_sym_b
     return WL_ERR_UNSUPPORTED;
 }
-int wl_dtinv1_strip(const WlDtInv1Args<float>& f, void* stream) { return wl_dtinv1_strip_any<float>(f, stream); }
-int wl_dtinv1_strip(const WlDtInv1Args<wl_half>& f, void* stream) { return wl_dtinv1_strip_any<wl_half>(f, stream); }
-int wl_dtinv1_strip(const WlDtInv1Args<wl_bf16>& f, void* stream) { return wl_dtinv1_strip_any<wl_bf16>(f, stream); }
-int wl_dtinv1_strip(const WlDtInv1Args<double>&, void*) { return WL_ERR_UNSUPPORTED; }
+WL_DT_INSTANTIATE(wl_dtinv1_strip, WlDtInv1Args, void*)
 
 // ---- levels 1 + 2 of the DTCWT forward in one streaming launch (wl_dtcwt_fused.h) ----------------------------------------
 #include "wl_dtcwt_fused.h"
@@ -599,25 +600,13 @@ static int wl_dtfwd12_launch(WlDtFusedArgs<T>& a, void* stream) {
 }
 
 template <typename T>
-static int wl_dtfwd12_any(const void* x, void* highs1, void* ll2, void* highs2, int64_t planes, int H, int W, const void* h0o,
-                          int L0, const void* h1o, int L1, const void* h0a, const void* h0b, const void* h1a,
-                          const void* h1b, int LQ, int policy, void* stream) {
-    typedef typename WlAcc<T>::type A;
+static int wl_dtfwd12_any(WlDtFusedArgs<T>& a, int LQ, int policy, void* stream) {
     const int SZ = (int)sizeof(T);
-    WlDtFusedArgs<T> a;
-    WlDtFwd1Args<T>& f = a.f;
-    f.x = (const T*)x; f.ll = nullptr; f.highs = (T*)highs1; f.z = nullptr; f.drdx = f.drdy = nullptr;
-    f.z_bs = f.z_ll_off = f.z_mag_off = 0;
-    f.h0 = (const A*)h0o; f.h1 = (const A*)h1o;
-    f.NC = planes; f.C = 1; f.H = H; f.W = W; f.He = H; f.We = W;
-    f.L0 = L0; f.L1 = L1; f.M = (L0 > L1 ? L0 : L1) / 2; f.ext = WL_EXT_SYM;
-    f.TH = f.TW = f.tiles_x = f.tiles_y = 0; f.nblocks = 0; f.run_len = f.runs_x = 0;
-    f.combine = 0; f.magbias = (A)0;
-    a.ll2 = (T*)ll2; a.highs2 = (T*)highs2;
-    a.h0a = (const float*)h0a; a.h0b = (const float*)h0b; a.h1a = (const float*)h1a; a.h1b = (const float*)h1b;
-    a.h2 = nullptr; a.L2 = 0;
+    const WlDtFwd1Args<T>& f = a.f;
+    const int64_t planes = f.NC;
+    const int H = f.H, W = f.W, L0 = f.L0, L1 = f.L1;
     if ((H % 4) || (W % 4) || H < 32 || W < 32 || (int64_t)H * W >= (1LL << 28)) return WL_ERR_UNSUPPORTED;
-    if ((uintptr_t)x % SZ || (uintptr_t)highs1 % (2 * SZ) || (uintptr_t)ll2 % (2 * SZ) || (uintptr_t)highs2 % (2 * SZ)) return WL_ERR_UNSUPPORTED;
+    if ((uintptr_t)f.x % SZ || (uintptr_t)f.highs % (2 * SZ) || (uintptr_t)a.ll2 % (2 * SZ) || (uintptr_t)a.highs2 % (2 * SZ)) return WL_ERR_UNSUPPORTED;
     // small work: per-level kernels.  (224-column planes only in numbers: 256x3x224^2 J = 2 forward 0.232 -> 0.190 ms, 128x3x224^2 0.111 -> 0.112,
     // 64x3x224^2 0.053 -> 0.059 - tools/gpu_r5z.py)
     if (!policy && (planes * (int64_t)wl_cdiv(H, 64) < wl_num_cus() || (W < 256 && !(W >= 224 && planes >= 3 * (int64_t)wl_num_cus())))) return WL_ERR_UNSUPPORTED;
@@ -638,17 +627,19 @@ extern "C" int wl_dtcwt_fwd_level12(const void* x, void* highs1, void* ll2, void
     if (mode != 1) return WL_ERR_UNSUPPORTED;                   // symmetric (coldfilt / rowdfilt know nothing else)
     if (planes == 0) return 0;
     if (wl_streaming_off()) return WL_ERR_UNSUPPORTED;
-    WL_DISPATCH_FLOAT(dtype, return wl_dtfwd12_any<T>(x, highs1, ll2, highs2, planes, H, W, h0o, L0, h1o, L1, h0a, h0b, h1a, h1b, LQ,
-                                                      policy, stream));
+    WL_DISPATCH_FLOAT(dtype, {
+        WlDtFwd1Args<T> f = wl_dtfwd1_args<T>(x, planes, 1, H, W, h0o, L0, h1o, L1, WL_EXT_SYM);
+        f.highs = (T*)highs1;
+        WlDtFusedArgs<T> a = wl_dtfused_args<T>(f, (T*)ll2, (T*)highs2, h0a, h0b, h1a, h1b);
+        return wl_dtfwd12_any(a, LQ, policy, stream);
+    });
 }
 
 // ---- lean level-1 forward / ScatLayer forward on the stagers and level-1 lanes of the fused kernel (MODE 0 / 1) ----------
 template <typename T, int L0, int L1, int MODE, int CW, int PP = 1>
 static int wl_dtlean1_launch(const WlDtFwd1Args<T>& f, void* stream, const float* h2 = nullptr, int L2 = 0) {
     typedef WlDtFwd12Strip<T, L0, L1, 10, MODE, CW, PP> K;
-    WlDtFusedArgs<T> a;
-    a.f = f;
-    a.ll2 = a.highs2 = nullptr; a.h0a = a.h0b = a.h1a = a.h1b = nullptr;
+    WlDtFusedArgs<T> a = wl_dtfused_args<T>(f);
     a.h2 = h2; a.L2 = L2;                                       // (MODE 6)
     const int Q = f.W / 2;
     a.nstrips = wl_cdiv(Q, 64 * CW / PP);
@@ -680,7 +671,7 @@ static int wl_dtlean1_launch(const WlDtFwd1Args<T>& f, void* stream, const float
 }
 
 template <typename T>
-static int wl_dtlean1_any(const WlDtFwd1Args<T>& f, void* stream) {
+int wl_dtfwd1_lean(const WlDtFwd1Args<T>& f, void* stream) {
     const int SZ = (int)sizeof(T);
     if (f.combine || f.ext != WL_EXT_SYM || f.He != f.H || f.We != f.W || (f.H % 4) || (f.W % 4)) return WL_ERR_UNSUPPORTED;
     if (f.H < 32 || f.W < 32 || (int64_t)f.H * f.W >= (1LL << 28) || (uintptr_t)f.x % SZ) return WL_ERR_UNSUPPORTED;
@@ -713,7 +704,7 @@ static int wl_dtlean1_any(const WlDtFwd1Args<T>& f, void* stream) {
 // ScatLayer inference with the rotationally symmetric level-1 filters ('near_sym_b_bp': 13 / 19 / 19 taps, a third band-pass filter for the
 // diagonal sub-band) on the lean kernel (MODE 6); called by wl_dtfwd1_rot_run (wl_api.inc) before the tile kernel WlDtFwd1Rot.
 template <typename T>
-static int wl_dtrot_lean_any(const WlDtFwd1Args<T>& f, const void* h2, int L2, void* stream) {
+int wl_dtrot_lean(const WlDtFwd1Args<T>& f, const void* h2, int L2, void* stream) {
     const int SZ = (int)sizeof(T);
     if (!f.z || f.ll || f.highs || f.drdx || f.drdy || f.combine || f.ext != WL_EXT_SYM || f.He != f.H || f.We != f.W || (f.H % 4) || (f.W % 4)) return WL_ERR_UNSUPPORTED;
     if (f.H < 40 || f.W < 128 || (int64_t)f.H * f.W >= (1LL << 28) || (uintptr_t)f.x % SZ || !h2) return WL_ERR_UNSUPPORTED;
@@ -722,20 +713,14 @@ static int wl_dtrot_lean_any(const WlDtFwd1Args<T>& f, const void* h2, int L2, v
     if (f.W <= 256 && f.NC >= 2) return wl_dtlean1_launch<T, 13, 19, 6, 4, 2>(f, stream, (const float*)h2, L2);
     return wl_dtlean1_launch<T, 13, 19, 6, 4, 1>(f, stream, (const float*)h2, L2);
 }
-int wl_dtrot_lean(const WlDtFwd1Args<float>& f, const void* h2, int L2, void* stream) { return wl_dtrot_lean_any<float>(f, h2, L2, stream); }
-int wl_dtrot_lean(const WlDtFwd1Args<wl_half>& f, const void* h2, int L2, void* stream) { return wl_dtrot_lean_any<wl_half>(f, h2, L2, stream); }
-int wl_dtrot_lean(const WlDtFwd1Args<wl_bf16>& f, const void* h2, int L2, void* stream) { return wl_dtrot_lean_any<wl_bf16>(f, h2, L2, stream); }
-int wl_dtrot_lean(const WlDtFwd1Args<double>&, const void*, int, void*) { return WL_ERR_UNSUPPORTED; }
-int wl_dtfwd1_lean(const WlDtFwd1Args<float>& f, void* stream) { return wl_dtlean1_any<float>(f, stream); }
-int wl_dtfwd1_lean(const WlDtFwd1Args<wl_half>& f, void* stream) { return wl_dtlean1_any<wl_half>(f, stream); }
-int wl_dtfwd1_lean(const WlDtFwd1Args<wl_bf16>& f, void* stream) { return wl_dtlean1_any<wl_bf16>(f, stream); }
-int wl_dtfwd1_lean(const WlDtFwd1Args<double>&, void*) { return WL_ERR_UNSUPPORTED; }
+WL_DT_INSTANTIATE(wl_dtrot_lean, WlDtFwd1Args, const void*, int, void*)
+WL_DT_INSTANTIATE(wl_dtfwd1_lean, WlDtFwd1Args, void*)
 
 // ---- streaming level >= 2 DTCWT inverse over column strips (wl_dtcwt_fused.h) ----------------------------------------------
 template <typename T, int LQ>
 static int wl_dtinv2_strip_launch(const WlDtInv2Args<T>& f, void* stream) {
     typedef WlDtInv2Strip<T, LQ> K;
-    WlDtI2StripArgs<T> a;
+    WlDtI2StripArgs<T> a = {};
     a.f = f;
     const int W2 = f.w / 2, H2 = f.h / 2;
     // one quad per stager lane: a strip's own quad columns and, towards a neighbouring strip, D2 of its quad columns
@@ -759,7 +744,7 @@ static int wl_dtinv2_strip_launch(const WlDtInv2Args<T>& f, void* stream) {
 }
 
 template <typename T>
-static int wl_dtinv2_strip_any(const WlDtInv2Args<T>& f, void* stream) {
+int wl_dtinv2_strip(const WlDtInv2Args<T>& f, void* stream) {
     const int SZ = (int)sizeof(T);
     if (!f.ll || !f.highs) return WL_ERR_UNSUPPORTED;
     if ((f.w & 1) || (f.h & 1) || (uintptr_t)f.ll % (2 * SZ) || (uintptr_t)f.highs % (2 * SZ) || (uintptr_t)f.y % (2 * SZ) ||
@@ -773,29 +758,17 @@ static int wl_dtinv2_strip_any(const WlDtInv2Args<T>& f, void* stream) {
     if (f.L == 18) return wl_dtinv2_strip_launch<T, 18>(f, stream);       // qshift_d
     return WL_ERR_UNSUPPORTED;
 }
-int wl_dtinv2_strip(const WlDtInv2Args<float>& f, void* stream) { return wl_dtinv2_strip_any<float>(f, stream); }
-int wl_dtinv2_strip(const WlDtInv2Args<wl_half>& f, void* stream) { return wl_dtinv2_strip_any<wl_half>(f, stream); }
-int wl_dtinv2_strip(const WlDtInv2Args<wl_bf16>& f, void* stream) { return wl_dtinv2_strip_any<wl_bf16>(f, stream); }
-int wl_dtinv2_strip(const WlDtInv2Args<double>&, void*) { return WL_ERR_UNSUPPORTED; }
+WL_DT_INSTANTIATE(wl_dtinv2_strip, WlDtInv2Args, void*)
 
 // ---- level >= 2 forward alone on the stagers and level-2 lanes of the fused kernel (MODE 4) ------------------------------------
 template <typename T, int CW, int MODE = 4, int LQ = 10>
 static int wl_dtfwd2_lean_launch(const WlDtFwd2Args<T>& g, void* stream) {
     typedef WlDtFwd12Strip<T, 5, 7, LQ, MODE, CW> K;
-    typedef typename WlAcc<T>::type A;
-    WlDtFusedArgs<T> a;
-    WlDtFwd1Args<T>& f = a.f;
-    f.x = g.x; f.ll = nullptr; f.highs = nullptr; f.z = nullptr; f.drdx = f.drdy = nullptr;
-    f.h0 = f.h1 = nullptr;
-    f.NC = g.NC; f.C = 1; f.H = g.H; f.W = g.W; f.He = g.H; f.We = g.W;
-    f.L0 = f.L1 = 1; f.M = 0; f.ext = WL_EXT_SYM;
-    f.TH = f.TW = f.tiles_x = f.tiles_y = 0; f.nblocks = 0; f.run_len = f.runs_x = 0;
-    f.combine = 0; f.magbias = (A)0;
-    f.z_bs = f.z_ll_off = f.z_mag_off = 0;
+    // this launch has no level 1: of the level-1 struct its kernel reads the input, the sizes and - MODE 5 - where ScatLayerj2's second
+    // scale puts its entries; there are no level-1 taps to pass (the tap counts are the kernel's template arguments), so L0 = L1 = 1, M = 0
+    WlDtFwd1Args<T> f = wl_dtfwd1_args<T>(g.x, g.NC, 1, g.H, g.W, nullptr, 1, nullptr, 1, WL_EXT_SYM);
     if (MODE == 5) { f.z = g.z; f.z_bs = g.z_bs; f.z_ll_off = g.z_ll_off; f.z_mag_off = g.z_mag_off; f.C = g.C; f.magbias = g.magbias; }
-    a.ll2 = g.ll; a.highs2 = g.highs;
-    a.h0a = (const float*)g.h0a; a.h0b = (const float*)g.h0b; a.h1a = (const float*)g.h1a; a.h1b = (const float*)g.h1b;
-    a.h2 = nullptr; a.L2 = 0;
+    WlDtFusedArgs<T> a = wl_dtfused_args<T>(f, g.ll, g.highs, g.h0a, g.h0b, g.h1a, g.h1b);
     const int Q = g.W / 2;
     a.nstrips = wl_cdiv(Q, 64 * CW);
     a.strip_quads = wl_align_up(wl_cdiv(Q, a.nstrips), 2);
@@ -820,7 +793,7 @@ static int wl_dtfwd2_lean_launch(const WlDtFwd2Args<T>& g, void* stream) {
 }
 
 template <typename T>
-static int wl_dtfwd2_lean_any(const WlDtFwd2Args<T>& g, void* stream) {
+int wl_dtfwd2_lean(const WlDtFwd2Args<T>& g, void* stream) {
     const int SZ = (int)sizeof(T);
     if ((!g.highs && !g.z) || (g.L != 10 && g.L != 14) || g.padr || g.padc || (g.H % 4) || (g.W % 4) || g.H < 32 || g.W < 32) return WL_ERR_UNSUPPORTED;
     if ((int64_t)g.H * g.W >= (1LL << 28) || (uintptr_t)g.x % SZ || (uintptr_t)g.ll % (2 * SZ) || (uintptr_t)g.highs % (2 * SZ)) return WL_ERR_UNSUPPORTED;
@@ -837,8 +810,6 @@ static int wl_dtfwd2_lean_any(const WlDtFwd2Args<T>& g, void* stream) {
     if (g.z) return g.W <= 256 ? wl_dtfwd2_lean_launch<T, 2, 5>(g, stream) : wl_dtfwd2_lean_launch<T, 4, 5>(g, stream);
     return g.W <= 256 ? wl_dtfwd2_lean_launch<T, 2>(g, stream) : wl_dtfwd2_lean_launch<T, 4>(g, stream);
 }
-int wl_dtfwd2_lean(const WlDtFwd2Args<float>& g, void* stream) { return wl_dtfwd2_lean_any<float>(g, stream); }
-int wl_dtfwd2_lean(const WlDtFwd2Args<wl_half>& g, void* stream) { return wl_dtfwd2_lean_any<wl_half>(g, stream); }
-int wl_dtfwd2_lean(const WlDtFwd2Args<wl_bf16>& g, void* stream) { return wl_dtfwd2_lean_any<wl_bf16>(g, stream); }
-int wl_dtfwd2_lean(const WlDtFwd2Args<double>&, void*) { return WL_ERR_UNSUPPORTED; }
+WL_DT_INSTANTIATE(wl_dtfwd2_lean, WlDtFwd2Args, void*)
+#undef WL_DT_INSTANTIATE
 #endif   // WL_STRIP_PARTS & 4

@@ -1,10 +1,11 @@
-"""The return codes of the 2-D DWT entry points (and of the other entries that share their dtype dispatch) for invalid
-arguments, on the host emulation with a chip of 8 compute units.  The Python layer never passes such arguments, so nothing
+"""The return codes of the 2-D DWT entry points, of the other entries that share their dtype dispatch and of the per-level
+DTCWT / ScatLayer entries for invalid arguments, on the host emulation with a chip of 8 compute units.  The Python layer never passes such arguments, so nothing
 else sees the validation at the top of the entries or the ORDER of its checks.
 
 Every entry starts from one valid small call (3 planes of 20 x 24, 4 taps, symmetric, float32, forced onto its kernel; real
 tensors behind every pointer) that returns 0, and is then called with one mutation at a time - or a pair, which pins which
-check comes first.  EXPECTED is what the library returned before the launchers took one request struct: a literal table."""
+check comes first.  EXPECTED is what the library returned before the launchers took one request struct (the DWT entries) or
+the typed argument struct of their kernel (the DTCWT / ScatLayer entries): a literal table."""
 import ctypes as C
 
 import pytest
@@ -25,6 +26,7 @@ def _buf():
 _KEEP = [_buf() for _ in range(12)]
 X, LL, HI, Y, HI2 = (t.data_ptr() for t in _KEEP[:5])
 T0, T1, T2, T3, T4, T5 = (t.data_ptr() for t in _KEEP[5:11])
+Z = _KEEP[11].data_ptr()
 TAPS4 = dict(t0=T0, t1=T1, t2=T2, t3=T3)
 
 # entry -> (argument names in the order of the prototype, the valid call, generic name -> the entry's own argument(s),
@@ -92,6 +94,67 @@ ENTRIES = {
         dict(x=X, highs1=HI, ll2=LL, highs2=HI2, dtype=F32, planes=3, H=32, W=32, L0=5, L1=7, LQ=10, mode=1, policy=1,
              t4=T4, t5=T5, **TAPS4),
         dict(L='L0'), {'policy=2': dict(policy=2), 'LQ=12': dict(LQ=12)}),
+    # the per-level DTCWT / ScatLayer entries: 3 planes of 32 x 32 (one image of three channels where the entry counts both),
+    # near_sym_a / qshift_a tap counts, symmetric, float32
+    'wl_dtcwt_fwd_level1': (
+        'x ll highs dtype planes H W t0 L0 t1 L1 mode stream',
+        dict(x=X, ll=LL, highs=HI, dtype=F32, planes=3, H=32, W=32, t0=T0, L0=5, t1=T1, L1=7, mode=1),
+        dict(L=('L0', 'L1')), {'mode=7': dict(mode=7), 'L0=4': dict(L0=4), 'mode=7,L0=4': dict(mode=7, L0=4),
+                                'H=0,L0=4': dict(H=0, L0=4), 'L=129,L0=4': dict(L1=129, L0=4), 'L0=4,dtype=99': dict(L0=4, dtype=99)}),
+    'wl_scat_fwd_level1': (
+        'x z drdx drdy ll dtype N C H W t0 L0 t1 L1 mode magbias combine stream',
+        dict(x=X, z=Z, drdx=HI, drdy=HI2, ll=LL, dtype=F32, N=1, C=3, H=32, W=32, t0=T0, L0=5, t1=T1, L1=7, mode=1, magbias=0.01,
+             combine=0),
+        dict(L=('L0', 'L1'), planes='N'),
+        {'mode=7': dict(mode=7), 'L0=4': dict(L0=4), 'combine,C=2': dict(combine=1, C=2), 'mode=7,C=0': dict(mode=7, C=0),
+         'combine,C=2,L=0': dict(combine=1, C=2, L0=0, L1=0), 'L=129,L0=4': dict(L1=129, L0=4), 'L0=4,dtype=99': dict(L0=4, dtype=99)}),
+    'wl_scat_fwd_level1_into': (
+        'x z z_bs z_ll z_mag ll dtype N C H W t0 L0 t1 L1 mode magbias stream',
+        dict(x=X, z=Z, z_bs=7 * 3 * 256, z_ll=0, z_mag=3 * 256, ll=LL, dtype=F32, N=1, C=3, H=32, W=32, t0=T0, L0=5, t1=T1, L1=7,
+             mode=1, magbias=0.01),
+        dict(L=('L0', 'L1'), planes='N'),
+        {'mode=7': dict(mode=7), 'L0=4': dict(L0=4), 'z=NULL': dict(z=None), 'mode=7,z=NULL': dict(mode=7, z=None),
+         'z=NULL,L=0': dict(z=None, L0=0, L1=0), 'L=129,L0=4': dict(L1=129, L0=4), 'L0=4,dtype=99': dict(L0=4, dtype=99)}),
+    # (the second scale of ScatLayerj2 has the streaming kernel only, which takes planes of 128 columns and more that fill the
+    # chip: its valid call is 8 planes of 32 x 128)
+    'wl_scat_fwd_level2_into': (
+        'x z z_bs z_ll z_mag dtype N C H W t0 t1 t2 t3 L magbias stream',
+        dict(x=X, z=Z, z_bs=7 * 8 * 256, z_ll=0, z_mag=8 * 256, dtype=F32, N=1, C=8, H=32, W=128, L=10, magbias=0.01, **TAPS4),
+        dict(planes='N'),
+        {'L=11': dict(L=11), 'H=34': dict(H=34), 'z=NULL': dict(z=None), 'z=NULL,L=11': dict(z=None, L=11),
+         'H=34,L=11': dict(H=34, L=11), 'H=34,dtype=99': dict(H=34, dtype=99), '3 planes of 32 x 32': dict(C=3, W=32)}),
+    # (near_sym_b_bp: 13 / 19 / 19 taps)
+    'wl_dtcwt_fwd_level1_rot': (
+        'x ll re im dtype N C H W t0 L0 t1 L1 t2 L2 mode scat magbias stream',
+        dict(x=X, ll=LL, re=HI, im=HI2, dtype=F32, N=1, C=3, H=32, W=32, t0=T0, L0=13, t1=T1, L1=19, t2=T2, L2=19, mode=1, scat=0,
+             magbias=0.01),
+        dict(L=('L0', 'L1', 'L2'), planes='N'),
+        {'mode=7': dict(mode=7), 'L0=4': dict(L0=4), 'L2=21': dict(L2=21), 'H=31': dict(H=31), 'L2=129': dict(L2=129),
+         'mode=7,C=0': dict(mode=7, C=0), 'L2=21,dtype=99': dict(L2=21, dtype=99), 'H=31,dtype=99': dict(H=31, dtype=99),
+         'L2=129,L0=4': dict(L2=129, L0=4)}),
+    'wl_dtcwt_fwd_level2': (
+        'x ll highs dtype planes H W t0 t1 t2 t3 L stream',
+        dict(x=X, ll=LL, highs=HI, dtype=F32, planes=3, H=32, W=32, L=10, **TAPS4), {},
+        {'L=11': dict(L=11), 'H=31': dict(H=31), 'H=31,L=11': dict(H=31, L=11), 'L=11,dtype=99': dict(L=11, dtype=99)}),
+    'wl_dtcwt_inv_level1': (
+        'll ll_ps ll_rs highs y dtype planes H W t0 L0 t1 L1 mode stream',
+        dict(ll=LL, ll_ps=1024, ll_rs=32, highs=HI, y=Y, dtype=F32, planes=3, H=32, W=32, t0=T0, L0=7, t1=T1, L1=5, mode=1),
+        dict(L=('L0', 'L1')),
+        {'L0=4': dict(L0=4), 'H=31': dict(H=31), 'll=highs=NULL': dict(ll=None, highs=None),
+         'll=highs=NULL,L=0': dict(ll=None, highs=None, L0=0, L1=0), 'L=129,L0=4': dict(L1=129, L0=4),
+         'L0=4,dtype=99': dict(L0=4, dtype=99)}),
+    'wl_scat_bwd_level1': (
+        'dz drdx drdy dx dtype N C H W t0 L0 t1 L1 mode combine stream',
+        dict(dz=Z, drdx=HI, drdy=HI2, dx=Y, dtype=F32, N=1, C=3, H=32, W=32, t0=T0, L0=5, t1=T1, L1=7, mode=1, combine=0),
+        dict(L=('L0', 'L1'), planes='N'),
+        {'mode=7': dict(mode=7), 'L0=4': dict(L0=4), 'H=31': dict(H=31), 'combine,C=2': dict(combine=1, C=2),
+         'mode=7,H=31': dict(mode=7, H=31), 'combine,C=2,L=0': dict(combine=1, C=2, L0=0, L1=0)}),
+    'wl_dtcwt_inv_level2': (
+        'll ll_ps ll_rs highs y dtype planes h w t0 t1 t2 t3 L stream',
+        dict(ll=LL, ll_ps=256, ll_rs=16, highs=HI, y=Y, dtype=F32, planes=3, h=16, w=16, L=10, **TAPS4),
+        dict(H='h'),
+        {'L=11': dict(L=11), 'h=15': dict(h=15), 'll=highs=NULL': dict(ll=None, highs=None),
+         'll=highs=NULL,L=11': dict(ll=None, highs=None, L=11), 'L=11,dtype=99': dict(L=11, dtype=99)}),
 }
 
 # generic mutations: name -> {generic argument: value}; an entry takes those whose arguments it has
@@ -105,8 +168,14 @@ GENERIC = {
 # (8 x 3 planes = 3 x 8 compute units is exactly where the fused kernels start to pay: 'not forced, 3 planes' is a launch
 # there, recorded as such; the same with 2 planes is the decline)
 LAUNCHES = 'not forced, 3 planes'
-# float64 is a valid dtype of the three per-level entries - their generic kernels take it: only the unknown dtype there
-F64_LAUNCHES = {'wl_dwt2d_analysis', 'wl_dwt2d_analysis_strided', 'wl_dwt2d_synthesis'}
+# float64 is a valid dtype of the per-level entries that have a generic kernel: only the unknown dtype there
+F64_LAUNCHES = {'wl_dwt2d_analysis', 'wl_dwt2d_analysis_strided', 'wl_dwt2d_synthesis', 'wl_dtcwt_fwd_level1',
+                'wl_scat_fwd_level1', 'wl_scat_fwd_level1_into', 'wl_dtcwt_fwd_level1_rot', 'wl_dtcwt_fwd_level2',
+                'wl_dtcwt_inv_level1', 'wl_dtcwt_inv_level2'}
+# mode 3 (and 5) is a padding mode of the level-1 DTCWT / ScatLayer entries (zeros, like every mode but symmetric), and the
+# level-1 inverse takes any: a launch there - their invalid mode is 'mode=7'
+MODE3_LAUNCHES = {'wl_dtcwt_fwd_level1', 'wl_scat_fwd_level1', 'wl_scat_fwd_level1_into', 'wl_dtcwt_fwd_level1_rot',
+                  'wl_dtcwt_inv_level1', 'wl_scat_bwd_level1'}
 
 EXPECTED = {
     'wl_dwt2d_analysis': {
@@ -167,6 +236,50 @@ EXPECTED = {
         'dtype=99': DTYPE, 'policy=4': UNSUP, 'mode=3,L=0': TAPS, 'H=0,L=0': SHAPE, 'L=0,dtype=99': TAPS, 'policy=2': UNSUP,
         'LQ=12': UNSUP
     },
+    'wl_dtcwt_fwd_level1': {
+        'valid': 0, 'planes=-1': SHAPE, 'H=0': SHAPE, 'L=0': TAPS, 'L=129': TAPS, 'dtype=99': DTYPE, 'mode=3,L=0': TAPS,
+        'H=0,L=0': SHAPE, 'L=0,dtype=99': TAPS, 'mode=7': MODE, 'L0=4': UNSUP, 'mode=7,L0=4': MODE, 'H=0,L0=4': SHAPE,
+        'L=129,L0=4': TAPS, 'L0=4,dtype=99': UNSUP
+    },
+    'wl_scat_fwd_level1': {
+        'valid': 0, 'planes=-1': SHAPE, 'H=0': SHAPE, 'L=0': TAPS, 'L=129': TAPS, 'dtype=99': DTYPE, 'mode=3,L=0': TAPS,
+        'H=0,L=0': SHAPE, 'L=0,dtype=99': TAPS, 'mode=7': MODE, 'L0=4': UNSUP, 'combine,C=2': SHAPE, 'mode=7,C=0': MODE,
+        'combine,C=2,L=0': SHAPE, 'L=129,L0=4': TAPS, 'L0=4,dtype=99': UNSUP
+    },
+    'wl_scat_fwd_level1_into': {
+        'valid': 0, 'planes=-1': SHAPE, 'H=0': SHAPE, 'L=0': TAPS, 'L=129': TAPS, 'dtype=99': DTYPE, 'mode=3,L=0': TAPS,
+        'H=0,L=0': SHAPE, 'L=0,dtype=99': TAPS, 'mode=7': MODE, 'L0=4': UNSUP, 'z=NULL': SHAPE, 'mode=7,z=NULL': MODE,
+        'z=NULL,L=0': SHAPE, 'L=129,L0=4': TAPS, 'L0=4,dtype=99': UNSUP
+    },
+    'wl_scat_fwd_level2_into': {
+        'valid': 0, 'planes=-1': SHAPE, 'H=0': SHAPE, 'L=0': TAPS, 'L=129': TAPS, 'dtype=f64': UNSUP, 'dtype=99': DTYPE,
+        'H=0,L=0': SHAPE, 'L=0,dtype=99': TAPS, 'L=11': TAPS, 'H=34': UNSUP, 'z=NULL': SHAPE, 'z=NULL,L=11': SHAPE,
+        'H=34,L=11': TAPS, 'H=34,dtype=99': UNSUP, '3 planes of 32 x 32': UNSUP
+    },
+    'wl_dtcwt_fwd_level1_rot': {
+        'valid': 0, 'planes=-1': SHAPE, 'H=0': SHAPE, 'L=0': TAPS, 'L=129': TAPS, 'dtype=99': DTYPE, 'mode=3,L=0': TAPS,
+        'H=0,L=0': SHAPE, 'L=0,dtype=99': TAPS, 'mode=7': MODE, 'L0=4': UNSUP, 'L2=21': UNSUP, 'H=31': UNSUP, 'L2=129':
+        TAPS, 'mode=7,C=0': MODE, 'L2=21,dtype=99': UNSUP, 'H=31,dtype=99': UNSUP, 'L2=129,L0=4': TAPS
+    },
+    'wl_dtcwt_fwd_level2': {
+        'valid': 0, 'planes=-1': SHAPE, 'H=0': SHAPE, 'L=0': TAPS, 'L=129': TAPS, 'dtype=99': DTYPE, 'H=0,L=0': SHAPE,
+        'L=0,dtype=99': TAPS, 'L=11': TAPS, 'H=31': SHAPE, 'H=31,L=11': SHAPE, 'L=11,dtype=99': TAPS
+    },
+    'wl_dtcwt_inv_level1': {
+        'valid': 0, 'planes=-1': SHAPE, 'H=0': SHAPE, 'L=0': TAPS, 'L=129': TAPS, 'dtype=99': DTYPE, 'mode=3,L=0': TAPS,
+        'H=0,L=0': SHAPE, 'L=0,dtype=99': TAPS, 'L0=4': UNSUP, 'H=31': SHAPE, 'll=highs=NULL': SHAPE, 'll=highs=NULL,L=0':
+        SHAPE, 'L=129,L0=4': TAPS, 'L0=4,dtype=99': UNSUP
+    },
+    'wl_scat_bwd_level1': {
+        'valid': 0, 'planes=-1': SHAPE, 'H=0': SHAPE, 'L=0': TAPS, 'L=129': TAPS, 'dtype=f64': UNSUP, 'dtype=99': DTYPE,
+        'mode=3,L=0': TAPS, 'H=0,L=0': SHAPE, 'L=0,dtype=99': TAPS, 'mode=7': MODE, 'L0=4': UNSUP, 'H=31': SHAPE,
+        'combine,C=2': SHAPE, 'mode=7,H=31': MODE, 'combine,C=2,L=0': SHAPE
+    },
+    'wl_dtcwt_inv_level2': {
+        'valid': 0, 'planes=-1': SHAPE, 'H=0': SHAPE, 'L=0': TAPS, 'L=129': TAPS, 'dtype=99': DTYPE, 'H=0,L=0': SHAPE,
+        'L=0,dtype=99': TAPS, 'L=11': TAPS, 'h=15': SHAPE, 'll=highs=NULL': SHAPE, 'll=highs=NULL,L=11': SHAPE,
+        'L=11,dtype=99': TAPS
+    },
 }
 
 
@@ -174,7 +287,7 @@ def _mutations(entry):
     _, base, alias, extra = ENTRIES[entry]
     out = {}
     for label, change in GENERIC.items():
-        if label == 'dtype=f64' and entry in F64_LAUNCHES:
+        if (label == 'dtype=f64' and entry in F64_LAUNCHES) or (label == 'mode=3' and entry in MODE3_LAUNCHES):
             continue
         real = {}
         for k, v in change.items():
