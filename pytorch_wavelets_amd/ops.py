@@ -355,7 +355,9 @@ FUSED_STRIPS = 0   # default `strips` of the two streaming entry points below: 0
 # compute waves, LDS budget, schedule table, ...).  A decline depends on nothing but the key - every argument the launcher's
 # decision can depend on is part of it: device (CU count), dtype, plane count, sizes, strides, tap counts, mode / extension,
 # output placement - so the outputs of a doomed call are allocated once per configuration, not on every forward of the
-# n = 3, 2, 1 ladder of the callers.
+# n = 3, 2, 1 ladder of the callers.  The ADDRESS of an input is no part of a key: where a launcher declines a base it cannot
+# load from (afb2d_fused: 16 bytes; sfb2d_fused: 4 bytes; dtcwt_inv21: 2 * sizeof(T)), the wrapper tests it itself and returns
+# before the key is written - a view one element into its buffer must not reroute the aligned tensors of its shape.
 _FUSED_DECLINED = set()
 _FUSED_DECLINED_MAX = 4096
 
@@ -1217,6 +1219,11 @@ def dtcwt_inv21(ll2, highs2, highs1, g0o, g1o, g0a, g0b, g1a, g1b, mode, force=F
     if not force and key in _FUSED_DECLINED:
         return None
     highs2, highs1 = highs2.contiguous(), highs1.contiguous()
+    # the kernel loads pairs of elements (wl_dtinv21_any): a base that is not on 2 * sizeof(T) - a view one element into its
+    # buffer - is that tensor's affair, not the configuration's, and is declined here, where the memo does not hear of it
+    pair = 2 * ll2.element_size()
+    if ll2.data_ptr() % pair or highs2.data_ptr() % pair or highs1.data_ptr() % pair:
+        return None
     t0, t1 = _taps(g0o, ll2), _taps(g1o, ll2)
     ta, tb, tc, td = (_taps(g, ll2) for g in (g0a, g0b, g1a, g1b))
     y = torch.empty((N, C, 2 * h, 2 * w), dtype=ll2.dtype, device=ll2.device)
