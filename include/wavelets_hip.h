@@ -47,7 +47,9 @@ extern "C" {
  *          reached through the new *_ex entry points (tap_scratch + the caller-owned `tap_state`), and
  *          wl_dwt2d_analysis_fused_strided is gone (wl_dwt2d_analysis_fused_ex takes the strides).  A caller built against 2.0.0
  *          must be recompiled against this header (check wl_version() >= 210).
- *   220 (this header): dtype WL_BF16 (bfloat16 data, float taps) everywhere WL_F16 is accepted; no argument list changes. */
+ *   220 (this header): dtype WL_BF16 (bfloat16 data, float taps) everywhere WL_F16 is accepted; no argument list changes.
+ *          Later under 220, new names only: wl_dwt3d_depth_analysis / wl_dwt3d_depth_synthesis (the depth axis of the 3-D DWT;
+ *          a caller that needs them looks the symbols up). */
 int wl_version(void);
 const char* wl_backend(void);
 
@@ -434,6 +436,41 @@ int wl_corr1d_adj(const void* y0, int64_t y0_outer_stride, const void* y1, int64
  * ny <= 2K-L+2 (2K for periodization, whose single fold of the wrapped tail is reproduced literally). */
 int wl_synth1d(const void* lo, const void* hi, void* y, int dtype, int64_t outer, int K, int64_t inner, int ny,
                const void* g0, const void* g1, int L, int mode, void* stream);
+
+/* The depth axis of the 3-D DWT (csrc/wl_dwt3d.h): one analysis level along the MIDDLE axis of (outer, n, inner) data for up to
+ * four sources in ONE launch - the ll and the three high bands of the 2-D level that ran on the N*C*D planes of a volume.
+ * Element (o, p, i) of source s is   src[s][o * src_outer_stride[s] + p * src_axis_stride[s] + i]   (strides in elements, the
+ * `inner` elements of a plane contiguous), and its two outputs, K = wl_dwt_coeff_len(n, L, mode) planes each,
+ *   lo[s][o * lo_outer_stride[s] + k * lo_axis_stride[s] + i],  hi[s][...] = sum_j h0[j], h1[j] * ext(x, 2k + base + j)
+ * with the stored (reversed) float taps and the base of wl_dwt2d_analysis: what afb1d (dwt/lowlevel.py:91-172) computes along
+ * that axis.  The strides let the kernel read the dense ll (P,H',W') / highs (P,3,H',W') of the 2-D engine and write the final
+ * (N,C,D',H',W') / (N,C,7,D',H',W') tensors: no stack, cat or permute afterwards.  A thread streams along the axis with a window
+ * of L planes in registers: every input plane is read once per depth chunk.  chunks: 0 = the launcher's policy (the fewest
+ * chunks that give every compute unit work), c > 0 = exactly min(c, K) chunks (tests put chunk seams into tiny signals); the
+ * result does not depend on the cut, bit for bit.  16-byte accesses when inner, every stride and every base allow it, scalar
+ * ones otherwise.  float32 / float16 / bfloat16, even L0 == L1 <= 20, the five modes of wl_dwt2d_analysis.
+ * Returns WL_ERR_UNSUPPORTED for float64, odd or unequal tap counts, L > 20, periodization of a signal shorter than the filter
+ * (n + (n & 1) < L - 1: the reference folds the wrapped tail once, wl_corr1d's ext 6), n or inner >= 2^29 and grids beyond
+ * 2^31 - 1 workgroups: callers then run wl_corr1d per source. */
+int wl_dwt3d_depth_analysis(const void* const* src, const int64_t* src_outer_stride, const int64_t* src_axis_stride,
+                            void* const* lo, const int64_t* lo_outer_stride, const int64_t* lo_axis_stride,
+                            void* const* hi, const int64_t* hi_outer_stride, const int64_t* hi_axis_stride, int nsrc, int dtype,
+                            int64_t outer, int n, int64_t inner, const void* h0, int L0, const void* h1, int L1, int mode,
+                            int chunks, void* stream);
+
+/* The matching synthesis level (csrc/wl_dwt3d.h) for up to four band pairs in ONE launch: lo[s], hi[s] (outer, K, inner) through
+ * their strides (hi[s] NULL = zeros) -> y[s] (outer, ny, inner) through its strides,
+ *   y[p] = full[p + L - 2],  full[m] = sum_k lo[k] g0[m - 2k] + hi[k] g1[m - 2k]            ny <= 2K - L + 2, or
+ *   periodization: the wrapped tail folded back and the roll by L/2 - 1 of sfb1d (dwt/lowlevel.py:226-271),   ny <= 2K
+ * - wl_synth1d's rule; ny below the full length crops (the backward of the analysis: AFB1D.backward :409-424).  A window of L/2
+ * planes of each band in registers, one new plane of each and two output planes per step.  chunks as above (min(c, steps)
+ * chunks of output pairs).  Returns WL_ERR_UNSUPPORTED for float64, odd or unequal tap counts, L > 20, periodization with fewer
+ * outputs than taps (2K < L - 2), K or inner >= 2^29 and grids beyond 2^31 - 1 workgroups: callers then run wl_synth1d per pair. */
+int wl_dwt3d_depth_synthesis(const void* const* lo, const int64_t* lo_outer_stride, const int64_t* lo_axis_stride,
+                             const void* const* hi, const int64_t* hi_outer_stride, const int64_t* hi_axis_stride,
+                             void* const* y, const int64_t* y_outer_stride, const int64_t* y_axis_stride, int nsrc, int dtype,
+                             int64_t outer, int K, int64_t inner, int ny, const void* g0, int L0, const void* g1, int L1,
+                             int mode, int chunks, void* stream);
 
 #ifdef __cplusplus
 }

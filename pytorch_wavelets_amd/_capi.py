@@ -4,6 +4,8 @@ import ctypes as C
 P = C.c_void_p
 I = C.c_int
 L = C.c_int64
+PP = C.POINTER(P)     # an array of pointers (one per source / level)
+PL = C.POINTER(L)     # an array of strides
 
 PROTOTYPES = {
     'wl_version': (I, []),
@@ -49,6 +51,8 @@ PROTOTYPES = {
     'wl_corr1d': (I, [P, P, P, I, L, I, L, L, I, P, P, I, I, I, I, I, I, I, I, I, P]),
     'wl_corr1d_adj': (I, [P, L, P, L, P, I, L, I, L, I, P, P, I, I, I, I, C.c_double, P]),
     'wl_synth1d': (I, [P, P, P, I, L, I, L, I, P, P, I, I, P]),
+    'wl_dwt3d_depth_analysis': (I, [PP, PL, PL, PP, PL, PL, PP, PL, PL, I, I, L, I, L, P, I, P, I, I, I, P]),
+    'wl_dwt3d_depth_synthesis': (I, [PP, PL, PL, PP, PL, PL, PP, PL, PL, I, I, L, I, L, I, P, I, P, I, I, I, P]),
     'wl_scat_bwd_level1': (I, [P, P, P, P, I, L, I, I, I, P, I, P, I, I, I, P]),
 }
 

@@ -16,6 +16,7 @@
 #include "wl_filt1d.h"
 #include "wl_swt2d.h"
 #include "wl_iswt2d.h"
+#include "wl_dwt3d.h"
 #include "wl_dtcwt_kernels.h"
 #include "wl_dtcwt_tile.h"
 #include "wl_dtcwt_rot.h"
@@ -1181,3 +1182,5 @@ extern "C" int wl_synth1d(const void* lo, const void* hi, void* y, int dtype, in
     });
     return 0;
 }
+
+#include "wl_dwt3d_api.inc"

@@ -854,6 +854,181 @@ def sfb2d(ll, lh, hl, hh, filts, mode='zero'):
     return SFB2D.apply(ll, highs, g0_row, g1_row, g0_col, g1_col, mode_to_int(mode))
 
 
+# ---- the 3-D DWT: the 2-D engine on the N*C*D planes, then one depth level (csrc/wl_dwt3d.h) -------------------------
+# Sub-band s = 4 b_D + 2 b_W + b_H (b = 1: highpass) of a level: s = 0 is the low-pass, band s sits at yh[:, :, s - 1].  The 2-D
+# level's (ll, lh, hl, hh) = b_D-lowpass bands 0..3, so its dense outputs are the depth kernel's four sources as they are.
+def _depth_analysis(ll, highs, C, h0, h1, mode, chunks=0):
+    """ll (N, C*D, H', W') and highs (N, C*D, 3, H', W') of a 2-D level on the planes of a volume -> yl (N, C, D', H', W'),
+    yh (N, C, 7, D', H', W'): one launch of the depth analysis kernel that writes the final layout, or - where it declines -
+    ops.afb1d along the depth axis per band."""
+    N, CD, Kh, Kw = ll.shape
+    D = CD // C
+    Kd = ops.coeff_len(D, h0.numel(), mode)
+    ll = ll.contiguous()                  # (dense already, as the 2-D level leaves them; a cotangent may be any view)
+    highs = highs.contiguous().view(N, C, D, 3, Kh, Kw)
+    srcs = [ll.view(N, C, D, Kh, Kw)] + [highs[:, :, :, b] for b in range(3)]
+    yl = torch.empty((N, C, Kd, Kh, Kw), dtype=ll.dtype, device=ll.device)
+    yh = torch.empty((N, C, 7, Kd, Kh, Kw), dtype=ll.dtype, device=ll.device)
+    los = [yl] + [yh[:, :, b] for b in range(3)]
+    his = [yh[:, :, 3 + b] for b in range(4)]
+    if ops.afb_depth(srcs, h0, h1, mode, chunks=chunks, dim=2, out=(los, his)) is None:
+        for src, lo, hi in zip(srcs, los, his):
+            a, b = ops.afb1d(src, h0, h1, mode, 2)
+            lo.copy_(a)
+            hi.copy_(b)
+    return yl, yh
+
+
+def _depth_synthesis(yl, yh, g0, g1, mode, out_len=None, chunks=0):
+    """yl (N, C, K, H', W') and yh (N, C, 7, K, H', W') or None (zeros) -> the dense ll (N, C*D, H', W') and highs
+    (N, C*D, 3, H', W') (None without yh) that the 2-D synthesis takes, D = ops.synth_len(K) or out_len: one launch of the depth
+    synthesis kernel, or - where it declines - ops.sfb1d along the depth axis per band pair."""
+    N, C, K, Kh, Kw = yl.shape
+    D = ops.synth_len(K, g0.numel(), mode, out_len)
+    ll = torch.empty((N, C * D, Kh, Kw), dtype=yl.dtype, device=yl.device)
+    ys = [ll.view(N, C, D, Kh, Kw)]
+    los, his, highs = [yl], [None], None
+    if yh is not None:
+        if yh.dtype != yl.dtype:
+            yh = yh.to(yl.dtype)
+        if tuple(yh.shape) != (N, C, 7, K, Kh, Kw):
+            raise ValueError('yh %s does not match yl %s' % (tuple(yh.shape), tuple(yl.shape)))
+        highs = torch.empty((N, C * D, 3, Kh, Kw), dtype=yl.dtype, device=yl.device)
+        hv = highs.view(N, C, D, 3, Kh, Kw)
+        ys += [hv[:, :, :, b] for b in range(3)]
+        los += [yh[:, :, b] for b in range(3)]
+        his = [yh[:, :, 3 + b] for b in range(4)]
+    if ops.sfb_depth(los, his, g0, g1, mode, out_len=out_len, chunks=chunks, dim=2, out=ys) is None:
+        for lo, hi, y in zip(los, his, ys):
+            y.copy_(ops.sfb1d(lo, hi, g0, g1, mode, 2, out_len=out_len))
+    return ll, highs
+
+
+class AFBDepth(Function):
+    """The depth level of a 3-D analysis: ``AFBDepth.apply(ll, highs, h0_dep, h1_dep, mode_int, C) -> (yl, yh)`` takes the 2-D
+    level of the N*C*D planes (ll (N, C*D, H', W'), highs (N, C*D, 3, H', W')) to yl (N, C, D', H', W') and yh
+    (N, C, 7, D', H', W').  Backward = the depth synthesis with the same stored taps, cropped to the input depth: the reference's
+    convention for AFB2D.backward (dwt/lowlevel.py:350-365, quirk Q9) applied to the third axis, so that the three axes agree -
+    the exact adjoint in 'zero' mode."""
+
+    @staticmethod
+    def forward(ctx, ll, highs, h0, h1, mode, C):
+        _check_bank_mode(mode)
+        ctx.save_for_backward(h0, h1)
+        ctx.mode = mode
+        ctx.depth = ll.shape[1] // C
+        return _depth_analysis(ll, highs, C, h0, h1, mode)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dyl, dyh):
+        dll = dhighs = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            h0, h1 = ctx.saved_tensors
+            dll, dhighs = _depth_synthesis(dyl, dyh, h0, h1, ctx.mode, out_len=ctx.depth)
+        return dll, dhighs, None, None, None, None
+
+
+class SFBDepth(Function):
+    """The depth level of a 3-D synthesis: ``SFBDepth.apply(yl, yh, g0_dep, g1_dep, mode_int) -> (ll, highs)``, yh None = zeros
+    (highs is then None too).  Backward = the depth analysis with the stored synthesis taps (the reference's SFB2D.backward,
+    dwt/lowlevel.py:683-694, on the third axis)."""
+
+    @staticmethod
+    def forward(ctx, yl, yh, g0, g1, mode):
+        _check_bank_mode(mode)
+        ctx.save_for_backward(g0, g1)
+        ctx.mode = mode
+        ctx.has_highs = yh is not None
+        ctx.C = yl.shape[1]
+        ll, highs = _depth_synthesis(yl, yh, g0, g1, mode)
+        if highs is None:
+            return ll
+        return ll, highs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dll, dhighs=None):
+        dyl = dyh = None
+        if ctx.needs_input_grad[0] or (ctx.has_highs and ctx.needs_input_grad[1]):
+            g0, g1 = ctx.saved_tensors
+            if ctx.has_highs:
+                dyl, dyh = _depth_analysis(dll, dhighs, ctx.C, g0, g1, ctx.mode)
+            else:
+                N, CD, Kh, Kw = dll.shape
+                dyl = ops.afb1d(dll.reshape(N, ctx.C, CD // ctx.C, Kh, Kw), g0, g1, ctx.mode, 2)[0]
+        return dyl, dyh, None, None, None
+
+
+def _afb3d_level(x, dep, banks, mode):
+    """One 3-D analysis level: x (N, C, D, H, W) -> yl, yh; dep = (h0_dep, h1_dep), banks = the four 2-D banks in AFB2DMulti's
+    argument order (the first pair filters along W)."""
+    if x.dim() != 5:
+        raise ValueError('the 3-D transform takes (N, C, D, H, W) tensors, not %d-D ones' % x.dim())
+    N, C, D, H, W = x.shape
+    outs = AFB2DMulti.apply(x.reshape(N, C * D, H, W), banks[0], banks[1], banks[2], banks[3], mode, 1)
+    return AFBDepth.apply(outs[0], outs[1], dep[0], dep[1], mode, C)
+
+
+def _sfb3d_level(yl, yh, dep, banks, mode):
+    """One 3-D synthesis level (yh None = zeros): the 'unpad' of a low-pass one sample longer than the highs along any axis, the
+    depth synthesis, the 2-D synthesis of the planes."""
+    if yl.dim() != 5:
+        raise ValueError('the 3-D transform takes (N, C, D, H, W) tensors, not %d-D ones' % yl.dim())
+    if yh is not None:
+        for ax in (-3, -2, -1):
+            if yl.shape[ax] > yh.shape[ax]:
+                yl = yl.narrow(ax, 0, yl.shape[ax] - 1)
+    N, C = yl.shape[:2]
+    res = SFBDepth.apply(yl, yh, dep[0], dep[1], mode)
+    ll, highs = res if yh is not None else (res, None)
+    y = SFB2DMulti.apply(ll, banks[0], banks[1], banks[2], banks[3], mode, highs)
+    return y.reshape(N, C, ll.shape[1] // C, y.shape[-2], y.shape[-1])
+
+
+def prep_filt_afb3d(h0_dep, h1_dep, h0_col=None, h1_col=None, h0_row=None, h1_row=None, device=None):
+    """(h0_dep, h1_dep, h0_col, h1_col, h0_row, h1_row): the depth pair stored reversed with shape (1,1,L,1,1), the other four as
+    prep_filt_afb2d makes them (one pair given: the same wavelet on the three axes)."""
+    d0, d1 = prep_filt_afb1d(h0_dep, h1_dep, device)
+    if h0_col is None:
+        h0_col, h1_col = h0_dep, h1_dep
+    return (d0.reshape(1, 1, -1, 1, 1), d1.reshape(1, 1, -1, 1, 1)) + prep_filt_afb2d(h0_col, h1_col, h0_row, h1_row, device)
+
+
+def prep_filt_sfb3d(g0_dep, g1_dep, g0_col=None, g1_col=None, g0_row=None, g1_row=None, device=None):
+    """(g0_dep, g1_dep, g0_col, g1_col, g0_row, g1_row): synthesis taps as given, shapes as prep_filt_afb3d."""
+    d0, d1 = prep_filt_sfb1d(g0_dep, g1_dep, device)
+    if g0_col is None:
+        g0_col, g1_col = g0_dep, g1_dep
+    return (d0.reshape(1, 1, -1, 1, 1), d1.reshape(1, 1, -1, 1, 1)) + prep_filt_sfb2d(g0_col, g1_col, g0_row, g1_row, device)
+
+
+def _filts3d(filts, prep, device):
+    if len(filts) not in (2, 6):
+        raise ValueError("Unknown form for input filts")
+    if any(not isinstance(f, torch.Tensor) for f in filts):
+        return prep(*filts, device=device)
+    if len(filts) == 2:
+        f0, f1 = (f.reshape(-1) for f in filts)
+        return (f0.reshape(1, 1, -1, 1, 1), f1.reshape(1, 1, -1, 1, 1)) + _to_2d(f0, f1, f0, f1)
+    return tuple(filts)
+
+
+def afb3d(x, filts, mode='zero'):
+    """Function-level 3-D analysis of x (N, C, D, H, W): ``filts`` = (h0, h1) for the three axes or (h0_dep, h1_dep, h0_col,
+    h1_col, h0_row, h1_row) - arrays in pywt order (reversed here) or prepared tensors; as in afb2d the *col* pair filters
+    along H, the *row* pair along W.  Returns (yl (N, C, D', H', W'), yh (N, C, 7, D', H', W')), band s = 4 b_D + 2 b_W + b_H at
+    yh[:, :, s - 1]."""
+    h0_dep, h1_dep, h0_col, h1_col, h0_row, h1_row = _filts3d(filts, prep_filt_afb3d, x.device)
+    return _afb3d_level(x, (h0_dep, h1_dep), (h0_row, h1_row, h0_col, h1_col), mode_to_int(mode))
+
+
+def sfb3d(ll, highs, filts, mode='zero'):
+    """Function-level 3-D synthesis, the inverse of afb3d: ll (N, C, K, H', W'), highs (N, C, 7, K, H', W') or None."""
+    g0_dep, g1_dep, g0_col, g1_col, g0_row, g1_row = _filts3d(filts, prep_filt_sfb3d, ll.device)
+    return _sfb3d_level(ll, highs, (g0_dep, g1_dep), (g0_row, g1_row, g0_col, g1_col), mode_to_int(mode))
+
+
 # ---- filter preparation (buffer shapes/orders are part of the state_dict contract) -----------------
 def _vec(h, reverse, device):
     h = np.array(h, dtype=np.float64).ravel()

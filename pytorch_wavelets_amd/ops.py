@@ -1060,6 +1060,163 @@ def sfb1d(lo, hi, g0, g1, mode, dim, out_len=None):
     return y
 
 
+# ---------------------------------------------------------------------------------------------- the depth axis of the 3-D DWT
+def _axis_strides(t, dim):
+    """(outer stride, axis stride) in elements of t seen as (outer, n, inner) around axis `dim`: the axes behind `dim` packed, the
+    axis itself at any stride that clears a plane, the axes before it one uniformly spaced index - or None when t has no such
+    description.  (Strides of size-1 axes carry no information and are not consulted.)"""
+    shape, st = t.shape, t.stride()
+    inner = 1
+    for k in range(t.dim() - 1, dim, -1):
+        if shape[k] > 1 and st[k] != inner:
+            return None
+        inner *= shape[k]
+    as_ = st[dim] if shape[dim] > 1 else inner
+    if as_ < inner:
+        return None
+    os_, span = None, 1
+    for k in range(dim - 1, -1, -1):
+        if shape[k] == 1:
+            continue
+        if os_ is None:
+            os_ = st[k]
+            if os_ < 0:
+                return None
+        elif st[k] != os_ * span:
+            return None
+        span *= shape[k]
+    return (as_ * shape[dim] if os_ is None else os_), as_
+
+
+def _depth_views(ts, dim):
+    """Every tensor of `ts` (None stays None) with its (outer stride, axis stride) for the depth kernels - the tensor itself
+    where it is a plane-strided view, one dense copy otherwise."""
+    out, oss, ass = [], [], []
+    for t in ts:
+        if t is None:
+            out.append(None), oss.append(0), ass.append(0)
+            continue
+        st = _axis_strides(t, dim) if t.numel() else None
+        if st is None:
+            t = t.contiguous()
+            st = _axis_strides(t, dim) if t.numel() else (0, 0)
+        out.append(t), oss.append(st[0]), ass.append(st[1])
+    return out, oss, ass
+
+
+def _ptr_array(ts):
+    return (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+def _i64_array(vs):
+    return (ctypes.c_int64 * len(vs))(*vs)
+
+
+def _depth_out(ref, dim, K, count):
+    """`count` uninitialised tensors shaped like ref with K samples along `dim`, side by side in one allocation."""
+    shape = list(ref.shape)
+    shape[dim] = K
+    buf = torch.empty([count] + shape, dtype=ref.dtype, device=ref.device)
+    return [buf[i] for i in range(count)]
+
+
+def _depth_align(ts):
+    """What the launcher's choice between its 16-byte and its scalar body depends on besides sizes and strides: are all bases
+    16-byte aligned?  (Part of the decline keys: a decline never depends on it today, and must not be remembered across it.)"""
+    return all(t is None or t.data_ptr() % 16 == 0 for t in ts)
+
+
+def afb_depth(srcs, h0, h1, mode, chunks=0, dim=1, out=None):
+    """One analysis level along axis `dim` of up to four tensors of one shape in ONE launch of the streaming depth kernel
+    (wl_dwt3d_depth_analysis): srcs[s] (outer.., n, inner..) -> (los, his), lists of tensors with coeff_len(n) samples along `dim`,
+    taps = the stored (reversed) ones - what afb1d makes of each source.  The sources may be plane-strided views (the bands of
+    the 2-D engine's (P,3,H',W') highs, every 4th channel): the axes behind `dim` packed, `dim` and the axes before it at any
+    uniform stride; anything else is copied once.  `out` = (los, his): views to write into - the final layout of a transform
+    (same rule; the caller owns their shapes) - instead of fresh tensors.  chunks: 0 = the engine's policy, c > 0 = c depth chunks.
+    None when the kernel does not cover the configuration (float64, odd / unequal / more than 20 taps, periodization of a signal
+    shorter than the filter): callers run afb1d per source."""
+    nsrc = len(srcs)
+    if not 1 <= nsrc <= 4:
+        raise ValueError('afb_depth: one to four sources, not %d' % nsrc)
+    ref = srcs[0]
+    for t in srcs:
+        _check_tensor(t, 'src')
+        if t.shape != ref.shape or t.dtype != ref.dtype:
+            raise ValueError('afb_depth: sources differ in shape or dtype')
+    _same_device(*srcs)
+    dim = dim % ref.dim()
+    n, L = ref.shape[dim], h0.numel()
+    if (ref.dtype == torch.float64 or L % 2 or L > 20 or h1.numel() != L or ref.numel() == 0 or mode not in _MODE_TO_EXT
+            or (mode == 2 and n + (n & 1) < L - 1)):
+        return None
+    K = coeff_len(n, L, mode)
+    outer, inner = _outer_inner(ref.shape, dim)
+    srcs, s_os, s_as = _depth_views(srcs, dim)
+    if out is None:
+        both = _depth_out(ref, dim, K, 2 * nsrc)
+        los, his = both[:nsrc], both[nsrc:]
+    else:
+        los, his = list(out[0]), list(out[1])
+    l_st = [_axis_strides(t, dim) for t in los]
+    h_st = [_axis_strides(t, dim) for t in his]
+    if any(st is None for st in l_st + h_st):
+        raise ValueError('afb_depth: an output view is not plane-strided')
+    key = ('afb_depth', ref.device, ref.dtype, nsrc, outer, n, inner, tuple(s_os), tuple(s_as), tuple(l_st), tuple(h_st), L, mode,
+           chunks, _depth_align(srcs + los + his))
+    if key in _FUSED_DECLINED:
+        return None
+    t0, t1 = _taps(h0, ref), _taps(h1, ref)
+    if _declined(key, 'wl_dwt3d_depth_analysis', ref, _ptr_array(srcs), _i64_array(s_os), _i64_array(s_as),
+                 _ptr_array(los), _i64_array([st[0] for st in l_st]), _i64_array([st[1] for st in l_st]),
+                 _ptr_array(his), _i64_array([st[0] for st in h_st]), _i64_array([st[1] for st in h_st]),
+                 nsrc, _DTYPES[ref.dtype], outer, n, inner, t0.data_ptr(), L, t1.data_ptr(), L, mode, chunks, _stream(ref)):
+        return None
+    return los, his
+
+
+def sfb_depth(los, his, g0, g1, mode, out_len=None, chunks=0, dim=1, out=None):
+    """One synthesis level along axis `dim` of up to four band pairs in ONE launch of the streaming depth kernel
+    (wl_dwt3d_depth_synthesis): los[s], his[s] (outer.., K, inner..; his[s] None = zeros) -> [y_s] with synth_len(K) samples along
+    `dim`, or out_len of them (the crop of the analysis backward) - what sfb1d makes of each pair.  Views, `out` (a list of
+    views to write into) and `chunks` as for afb_depth.  None when the kernel does not cover the configuration: callers run
+    sfb1d per pair."""
+    nsrc = len(los)
+    if not 1 <= nsrc <= 4 or len(his) != nsrc:
+        raise ValueError('sfb_depth: one to four (lo, hi) pairs')
+    ref = los[0]
+    for t in list(los) + [h for h in his if h is not None]:
+        _check_tensor(t, 'band')
+        if t.shape != ref.shape or t.dtype != ref.dtype:
+            raise ValueError('sfb_depth: bands differ in shape or dtype')
+    _same_device(*los, *his)
+    dim = dim % ref.dim()
+    K, L = ref.shape[dim], g0.numel()
+    if (ref.dtype == torch.float64 or L % 2 or L > 20 or g1.numel() != L or ref.numel() == 0 or mode not in _MODE_TO_EXT
+            or (mode == 2 and 2 * K < L - 2)):
+        return None
+    ny = synth_len(K, L, mode, out_len)
+    if ny < 1:
+        return None
+    outer, inner = _outer_inner(ref.shape, dim)
+    los, l_os, l_as = _depth_views(los, dim)
+    his, h_os, h_as = _depth_views(his, dim)
+    ys = _depth_out(ref, dim, ny, nsrc) if out is None else list(out)
+    y_st = [_axis_strides(t, dim) for t in ys]
+    if any(st is None for st in y_st):
+        raise ValueError('sfb_depth: an output view is not plane-strided')
+    key = ('sfb_depth', ref.device, ref.dtype, nsrc, outer, K, inner, ny, tuple(l_os), tuple(l_as), tuple(h is None for h in his),
+           tuple(h_os), tuple(h_as), tuple(y_st), L, mode, chunks, _depth_align(los + his + ys))
+    if key in _FUSED_DECLINED:
+        return None
+    t0, t1 = _taps(g0, ref), _taps(g1, ref)
+    if _declined(key, 'wl_dwt3d_depth_synthesis', ref, _ptr_array(los), _i64_array(l_os), _i64_array(l_as),
+                 _ptr_array(his), _i64_array(h_os), _i64_array(h_as),
+                 _ptr_array(ys), _i64_array([st[0] for st in y_st]), _i64_array([st[1] for st in y_st]),
+                 nsrc, _DTYPES[ref.dtype], outer, K, inner, ny, t0.data_ptr(), L, t1.data_ptr(), L, mode, chunks, _stream(ref)):
+        return None
+    return ys
+
+
 # ---------------------------------------------------------------------------------------------- DTCWT
 def dtcwt_fwd1(x, h0, h1, mode, skip_hps=False):
     """Level-1 forward: x (N,C,H,W) -> ll (N,C,He,We), highs (N,C,6,He/2,We/2,2) or None."""
