@@ -49,7 +49,7 @@ extern "C" {
  *          must be recompiled against this header (check wl_version() >= 210).
  *   220 (this header): dtype WL_BF16 (bfloat16 data, float taps) everywhere WL_F16 is accepted; no argument list changes.
  *          Later under 220, new names only: wl_dwt3d_depth_analysis / wl_dwt3d_depth_synthesis (the depth axis of the 3-D DWT;
- *          a caller that needs them looks the symbols up). */
+ *          a caller that needs them looks the symbols up); wl_dtcwt1d_analysis / wl_dtcwt1d_synthesis (the 1-D DTCWT) likewise. */
 int wl_version(void);
 const char* wl_backend(void);
 
@@ -349,6 +349,28 @@ int wl_dwt1d_analysis_fused(const void* x, void* lo, void* const* highs, int dty
  * Even L <= 20, float32 / float16, every mode but periodization.  WL_ERR_UNSUPPORTED otherwise: callers chain wl_synth1d. */
 int wl_dwt1d_synthesis_fused(const void* lo, int n_lo, const void* const* highs, const int* n_hi, void* y, int out_len, int dtype,
                              int64_t rows, int J, const void* g0, const void* g1, int L, int mode, void* stream);
+
+/* The 1-D dual-tree complex wavelet transform along the last axis, up to four levels in ONE launch (csrc/wl_dtcwt1d.h).
+ * Level 1 = the two odd-length filters at full rate (an odd N gets a copy of its last sample first), every further level the
+ * q-shift pair (Ya[k], Yb[k]) of both trees; the highpass of a level is the complex band, written / read as flat rows of
+ * (real, imaginary) pairs.  qstart != 0: the first level of this launch is a q-shift level already (levels 5.. of a deeper
+ * transform run as a second launch on the lowpass of the first).  float32 / float16 / bfloat16, odd level-1 lengths up to 19,
+ * q-shift lengths 10 / 14 / 18; WL_ERR_UNSUPPORTED otherwise and for levels too short to mirror inside a chunk (callers compose
+ * wl_corr1d).  chunk: coarsest-level pairs (analysis) / output samples (synthesis) per workgroup, 0 = the engine's choice.
+ *   wl_dtcwt1d_analysis: x (rows,N) -> his[l] (rows,n_{l+1}) and los[l] (rows,n_{l+1}), l = 0..J-1, either NULL = not stored
+ *     (los[J-1] is required); pad[l] = end rule of the INPUT of level l+1: 0 none, 1 one replicated sample either side (the
+ *     transform, where a length is no multiple of 4), 2 one zero either side (backward of a synthesis level that cropped);
+ *     pad[0] must be 0 for a level-1 start.  n_1 = N + (N & 1), n_{l+1} = (n_l + 2 (pad[l] != 0)) / 2.
+ *   wl_dtcwt1d_synthesis: lo (rows,n_lo), his[l] (rows,n[l]) or NULL = zeros, finest first -> y (rows,out_len); rule[l] = end rule
+ *     of the OUTPUT of level l+1 (rule[0]: of y): 0 none, 1 drop the first and the last sample (the inverse transform), 2 drop them
+ *     and add them to their neighbours (backward of an analysis level that padded; on a level-1 y: the last sample only, an odd
+ *     input); rule[J]: 1 = lo has n[J-1] + 2 samples and is cropped on the way in. */
+int wl_dtcwt1d_analysis(const void* x, void* const* his, void* const* los, int dtype, int64_t rows, int N, int J, int qstart,
+                        const int* pad, const void* h0o, const void* h1o, int L0, int L1, const void* h0a, const void* h0b,
+                        const void* h1a, const void* h1b, int M, int chunk, void* stream);
+int wl_dtcwt1d_synthesis(const void* lo, int n_lo, const void* const* his, const int* n, const int* rule, void* y, int out_len,
+                         int dtype, int64_t rows, int J, int qstart, const void* g0o, const void* g1o, int L0, int L1,
+                         const void* g0a, const void* g0b, const void* g1a, const void* g1b, int M, int chunk, void* stream);
 
 /* ---- single-axis building blocks -------------------------------------------------------------------------------
  * One strided / dilated correlation with boundary extension along the middle axis of a dense (outer, n, inner) tensor:

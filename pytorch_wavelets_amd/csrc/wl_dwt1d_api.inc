@@ -167,3 +167,6 @@ extern "C" int wl_dwt1d_synthesis_fused(const void* lo, int n_lo, const void* co
         return wl_idwt1d_fused_any<T>(a, L, stream);
     });
 }
+
+// ---- fused multi-level 1-D DTCWT (wl_dtcwt1d.h): the same translation unit, in the HIP build and in the host emulation -----
+#include "wl_dtcwt1d_api.inc"

@@ -431,3 +431,175 @@ class FWD_J2PLUS_ROT(Function):
             h0a, h1a, h0b, h1b, h2a, h2b = ctx.saved_tensors
             dx = inv_j2plus_rot(dll, dre, dim, h0b, h1b, h0a, h1a, h2b, h2a, 1, 3, 4, ctx.mode)
         return (dx,) + (None,) * 7
+
+
+# ---------------------------------------------------------------------------------------------- 1-D DTCWT
+# One autograd node per group of up to four levels.  The forward of a node is one launch of the fused analysis (WlDt1dFwd) or
+# synthesis (WlDt1dInv) kernel, its backward one launch of the OTHER kernel with the stored taps of its own direction, the a and
+# b trees swapped at the q-shift levels (reference transform_funcs.py:361-413, 434-488 carried to one axis): where the analysis
+# padded, its backward folds the pad samples back by addition; where the synthesis cropped, its backward pads with zeros.
+# Configurations the kernels decline (float64, other tap counts, levels too short to mirror inside a chunk) take the same
+# structure composed of the single-axis primitives of dtcwt/lowlevel.py.
+def _cols(fn, x, *args):
+    """A column primitive of dtcwt/lowlevel.py along the LAST axis of x (..., n)."""
+    y = fn(x.reshape(1, -1, x.shape[-1], 1).transpose(1, 2).reshape(1, 1, x.shape[-1], -1), *args)
+    return y.reshape(y.shape[2], -1).t().contiguous().reshape(tuple(x.shape[:-1]) + (y.shape[2],))
+
+
+def _dt1d_pad(x, pad, odd):
+    if odd:
+        return torch.cat((x, x[..., -1:]), dim=-1)
+    if pad == ops.DT1D_PAD_REPL:
+        return torch.cat((x[..., :1], x, x[..., -1:]), dim=-1)
+    if pad == ops.DT1D_PAD_ZERO:
+        return torch.nn.functional.pad(x, (1, 1))
+    return x
+
+
+def _dt1d_rule(y, rule, level1):
+    if rule == ops.DT1D_RULE_NONE:
+        return y
+    if rule == ops.DT1D_RULE_CROP:
+        return y[..., 1:-1]
+    if level1:
+        z = y[..., :-1].clone()
+        z[..., -1] += y[..., -1]
+        return z
+    z = y[..., 1:-1].clone()
+    z[..., 0] += y[..., 0]
+    z[..., -1] += y[..., -1]
+    return z
+
+
+def dt1d_analysis(x, taps, pads, qstart, want_hi, want_lo, chunk=None):
+    """(los, his) of ops.dtcwt1d_fwd: the fused kernel, or - where it declines - the same levels on the single-axis primitives."""
+    res = ops.dtcwt1d_fwd(x, taps, pads, qstart, want_hi, want_lo, chunk)
+    if res is not None:
+        return res
+    from . import lowlevel
+    h0o, h1o, h0a, h0b, h1a, h1b = taps
+    J = len(pads)
+    los, his, lo = [None] * J, [None] * J, x.contiguous()
+    for l in range(J):
+        if l == 0 and not qstart:
+            xi = _dt1d_pad(lo, 0, lo.shape[-1] % 2 == 1)
+            hi = _cols(lowlevel.colfilter, xi, h1o) if want_hi[l] else None
+            lo = _cols(lowlevel.colfilter, xi, h0o)
+        else:
+            xi = _dt1d_pad(lo, pads[l], False)
+            hi = _cols(lowlevel.coldfilt, xi, h1b, h1a, True) if want_hi[l] else None
+            lo = _cols(lowlevel.coldfilt, xi, h0b, h0a, False)
+        his[l] = hi
+        if want_lo[l] or l == J - 1:
+            los[l] = lo
+    return los, his
+
+
+def dt1d_synthesis(lo, his, ns, rules, out_len, taps, qstart, adds=None, chunk=None):
+    """y of ops.dtcwt1d_inv: the fused kernel, or the same levels on the single-axis primitives - where it declines, and where
+    `adds` (a tensor to add to the lowpass handed to level l + 1's finer neighbour: the cotangent of a scale) is given."""
+    J = len(his)
+    if adds is None or all(a is None for a in adds):
+        y = ops.dtcwt1d_inv(lo, his, ns, rules, out_len, taps, qstart, chunk)
+        if y is not None:
+            return y
+    from . import lowlevel
+    g0o, g1o, g0a, g0b, g1a, g1b = taps
+    lo = lo.contiguous()
+    if rules[J] == ops.DT1D_RULE_CROP:
+        lo = lo[..., 1:-1]
+    for l in range(J - 1, -1, -1):
+        if adds is not None and adds[l] is not None:
+            lo = lo + adds[l]
+        hi = his[l]
+        level1 = l == 0 and not qstart
+        if level1:
+            y = _cols(lowlevel.colfilter, lo, g0o)
+            if hi is not None:
+                y = y + _cols(lowlevel.colfilter, hi, g1o)
+        else:
+            y = _cols(lowlevel.colifilt, lo, g0b, g0a, False)
+            if hi is not None:
+                y = y + _cols(lowlevel.colifilt, hi, g1b, g1a, True)
+        lo = _dt1d_rule(y, rules[l], level1)
+    assert lo.shape[-1] == out_len
+    return lo
+
+
+def _swap_trees(taps):
+    o0, o1, a0, b0, a1, b1 = taps
+    return o0, o1, b0, a0, b1, a1
+
+
+class DTCWT1DAnalysis(Function):
+    """Up to four levels of the 1-D DTCWT analysis as one node: ``apply(x, h0o, h1o, h0a, h0b, h1a, h1b, qstart, skip, scale)``
+    with `skip` / `scale` tuples of bools over the levels -> ``(lo, hi_1 .. hi_J, lo_1 .. lo_J)``: hi_l (..., n_l) the flat
+    (real, imaginary) pairs or None where skipped, lo_l the lowpass of level l where `scale` asks for it, else None."""
+
+    @staticmethod
+    def forward(ctx, x, h0o, h1o, h0a, h0b, h1a, h1b, qstart, skip, scale):
+        J = len(skip)
+        taps = (h0o, h1o, h0a, h0b, h1a, h1b)
+        n = x.shape[-1]
+        pads = ops.dtcwt1d_pads(n, J, qstart)
+        los, his = dt1d_analysis(x, taps, pads, qstart, [not s for s in skip], list(scale))
+        ctx.save_for_backward(*taps)
+        ctx.plan = (n, pads, bool(qstart), ops.dtcwt1d_lengths(n, pads, qstart))
+        # (the last lowpass is returned once: as `lo`; its `scale` slot carries it again only through the module)
+        return (los[J - 1],) + tuple(his) + tuple(los[l] if scale[l] and l < J - 1 else None for l in range(J))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dlo, *rest):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 10
+        taps = ctx.saved_tensors
+        n, pads, qstart, ns = ctx.plan
+        J = len(pads)
+        dhis, dscales = list(rest[:J]), list(rest[J:])
+        ref = next(t for t in [dlo] + dhis + dscales if t is not None)
+        if dlo is None:
+            dlo = ref.new_zeros(tuple(ref.shape[:-1]) + (ns[J - 1],))
+        dhis = [None if d is None else d.reshape(tuple(d.shape[:-1]) + (ns[l],)) for l, d in enumerate(dhis)]
+        rules = [ops.DT1D_RULE_FOLD if pads[l] else ops.DT1D_RULE_NONE for l in range(J)] + [ops.DT1D_RULE_NONE]
+        if not qstart and n % 2:
+            rules[0] = ops.DT1D_RULE_FOLD
+        dx = dt1d_synthesis(dlo, dhis, ns, rules, n, _swap_trees(taps), qstart, adds=dscales)
+        return (dx,) + (None,) * 9
+
+
+class DTCWT1DSynthesis(Function):
+    """Up to four levels of the 1-D DTCWT synthesis as one node: ``apply(lo, g0o, g1o, g0a, g0b, g1a, g1b, qstart, ns, *his)``
+    with his[l] (..., ns[l]) the flat (real, imaginary) pairs or None (zeros), finest first -> y; a lowpass two samples longer
+    than a level's band loses its first and last sample on the way (the border the analysis added)."""
+
+    @staticmethod
+    def forward(ctx, lo, g0o, g1o, g0a, g0b, g1a, g1b, qstart, ns, *his):
+        J = len(his)
+        taps = (g0o, g1o, g0a, g0b, g1a, g1b)
+        rules = [ops.DT1D_RULE_NONE] * (J + 1)
+        assert lo.shape[-1] in (ns[J - 1], ns[J - 1] + 2), (lo.shape, ns)
+        if lo.shape[-1] != ns[J - 1]:
+            rules[J] = ops.DT1D_RULE_CROP
+        for l in range(1, J):
+            assert 2 * ns[l] in (ns[l - 1], ns[l - 1] + 2), ns
+            if 2 * ns[l] != ns[l - 1]:
+                rules[l] = ops.DT1D_RULE_CROP
+        out_len = 2 * ns[0] if qstart else ns[0]
+        ctx.save_for_backward(*taps)
+        ctx.plan = (tuple(ns), rules, bool(qstart), [h is not None for h in his])
+        return dt1d_synthesis(lo, list(his), ns, rules, out_len, taps, qstart)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        taps = ctx.saved_tensors
+        ns, rules, qstart, have = ctx.plan
+        J = len(ns)
+        pads = [ops.DT1D_PAD_ZERO if rules[l] == ops.DT1D_RULE_CROP else ops.DT1D_PAD_NONE for l in range(J)]
+        want_hi = [have[l] and ctx.needs_input_grad[9 + l] for l in range(J)]
+        los, dhis = dt1d_analysis(dy, _swap_trees(taps), pads, qstart, want_hi, [False] * J)
+        dlo = los[J - 1]
+        if rules[J] == ops.DT1D_RULE_CROP:
+            dlo = torch.nn.functional.pad(dlo, (1, 1))
+        return (dlo if ctx.needs_input_grad[0] else None,) + (None,) * 8 + tuple(dhis)

@@ -1216,6 +1216,108 @@ def sfb_depth(los, his, g0, g1, mode, out_len=None, chunks=0, dim=1, out=None):
         return None
     return ys
 
+# ---------------------------------------------------------------------------------------------- 1-D DTCWT
+DT1D_PAD_NONE, DT1D_PAD_REPL, DT1D_PAD_ZERO = 0, 1, 2
+DT1D_RULE_NONE, DT1D_RULE_CROP, DT1D_RULE_FOLD = 0, 1, 2
+DT1D_CHUNK = 0     # tests: a forced chunk length of the two fused kernels (0 = the engine's policy), to put seams into short signals
+
+
+def dtcwt1d_lengths(n, pads, qstart):
+    """Output lengths [n_1 ..] of the analysis levels of an n-sample signal whose level inputs carry the end rules `pads`
+    (pads[0] is ignored for a level-1 start: an odd n gets one more sample)."""
+    ns = []
+    for l, p in enumerate(pads):
+        n = n + (n & 1) if l == 0 and not qstart else (n + (2 if p else 0)) // 2
+        ns.append(n)
+    return ns
+
+
+def dtcwt1d_pads(n, J, qstart):
+    """The transform's own end rules: one replicated sample either side wherever a q-shift level's input is no multiple of 4."""
+    pads = []
+    for l in range(J):
+        if l == 0 and not qstart:
+            pads.append(DT1D_PAD_NONE)
+            n += n & 1
+        else:
+            pads.append(DT1D_PAD_REPL if n % 4 else DT1D_PAD_NONE)
+            n = (n + (2 if pads[-1] else 0)) // 2
+    return pads
+
+
+def _dt1d_covered(taps, J, qstart):
+    o0, o1, qa, qb, ra, rb = taps
+    if not qstart and (o0.numel() % 2 == 0 or o1.numel() % 2 == 0 or max(o0.numel(), o1.numel()) > 19):
+        return False
+    if J > 1 or qstart:
+        M = qa.numel()
+        return M in (10, 14, 18) and all(t.numel() == M for t in (qb, ra, rb))
+    return True
+
+
+def dtcwt1d_fwd(x, taps, pads, qstart, want_hi, want_lo, chunk=None):
+    """len(pads) (1..4) levels of the 1-D DTCWT analysis along the LAST axis in ONE launch (wl_dtcwt1d_analysis): x (..., n),
+    taps = (h0o, h1o, h0a, h0b, h1a, h1b) as stored -> (los, his), lists over the levels with None where want_lo / want_hi is
+    false (the last lowpass is always made); his[l] (..., n_l) = the flat (real, imaginary) pairs.  None when the kernel does
+    not cover the configuration (callers compose the single-axis primitives)."""
+    _check_tensor(x, 'x')
+    J, n = len(pads), x.shape[-1]
+    if x.dtype == torch.float64 or x.numel() == 0 or J < 1 or J > 4 or not _dt1d_covered(taps, J, qstart):
+        return None
+    chunk = DT1D_CHUNK if chunk is None else chunk
+    rows = x.numel() // n
+    pads = [DT1D_PAD_NONE if (l == 0 and not qstart) else int(p) for l, p in enumerate(pads)]
+    sizes = tuple(t.numel() for t in taps)
+    key = ('dt1d_fwd', x.device, x.dtype, rows, n, tuple(pads), bool(qstart), sizes, chunk)
+    if key in _FUSED_DECLINED:
+        return None
+    x = x.contiguous()
+    ns = dtcwt1d_lengths(n, pads, qstart)
+    lead = tuple(x.shape[:-1])
+    his = [torch.empty(lead + (ns[l],), dtype=x.dtype, device=x.device) if want_hi[l] else None for l in range(J)]
+    los = [torch.empty(lead + (ns[l],), dtype=x.dtype, device=x.device) if (want_lo[l] or l == J - 1) else None for l in range(J)]
+    tt = [_taps(t, x) for t in taps]
+    if _declined(key, 'wl_dtcwt1d_analysis', x, x.data_ptr(), _ptr_array(his), _ptr_array(los), _DTYPES[x.dtype], rows, n, J,
+                 int(bool(qstart)), (ctypes.c_int * J)(*pads), tt[0].data_ptr(), tt[1].data_ptr(), sizes[0], sizes[1],
+                 tt[2].data_ptr(), tt[3].data_ptr(), tt[4].data_ptr(), tt[5].data_ptr(), sizes[2], chunk, _stream(x)):
+        return None
+    return los, his
+
+
+def dtcwt1d_inv(lo, his, ns, rules, out_len, taps, qstart, chunk=None):
+    """len(his) (1..4) levels of the 1-D DTCWT synthesis along the LAST axis in ONE launch (wl_dtcwt1d_synthesis): lo (..., n_lo),
+    his[l] (..., ns[l]) flat (real, imaginary) pairs or None = zeros, finest first; rules[l] = end rule of the output of level
+    l + 1 (rules[0]: of y), rules[J]: CROP = lo carries one surplus sample either side; taps = (g0o, g1o, g0a, g0b, g1a, g1b).
+    Returns y (..., out_len), or None when the kernel does not cover the configuration."""
+    _check_tensor(lo, 'lo')
+    J = len(his)
+    if lo.dtype == torch.float64 or lo.numel() == 0 or J < 1 or J > 4 or not _dt1d_covered(taps, J, qstart):
+        return None
+    for h in his:
+        if h is not None:
+            _check_tensor(h, 'yh')
+            _same_device(lo, h)
+            if h.dtype != lo.dtype:
+                return None
+    chunk = DT1D_CHUNK if chunk is None else chunk
+    n_lo = lo.shape[-1]
+    rows = lo.numel() // n_lo
+    sizes = tuple(t.numel() for t in taps)
+    key = ('dt1d_inv', lo.device, lo.dtype, rows, n_lo, tuple(ns), tuple(rules), out_len, bool(qstart), sizes, chunk)
+    if key in _FUSED_DECLINED:
+        return None
+    lo = lo.contiguous()
+    his = [None if h is None else h.contiguous() for h in his]
+    y = torch.empty(tuple(lo.shape[:-1]) + (out_len,), dtype=lo.dtype, device=lo.device)
+    tt = [_taps(t, lo) for t in taps]
+    if _declined(key, 'wl_dtcwt1d_synthesis', lo, lo.data_ptr(), n_lo, _ptr_array(his), (ctypes.c_int * J)(*ns),
+                 (ctypes.c_int * (J + 1))(*rules), y.data_ptr(), out_len, _DTYPES[lo.dtype], rows, J, int(bool(qstart)),
+                 tt[0].data_ptr(), tt[1].data_ptr(), sizes[0], sizes[1], tt[2].data_ptr(), tt[3].data_ptr(), tt[4].data_ptr(),
+                 tt[5].data_ptr(), sizes[2], chunk, _stream(lo)):
+        return None
+    return y
+
+
 
 # ---------------------------------------------------------------------------------------------- DTCWT
 def dtcwt_fwd1(x, h0, h1, mode, skip_hps=False):
