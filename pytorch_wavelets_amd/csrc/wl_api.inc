@@ -403,7 +403,7 @@ WL_FUNCTOR(WlDtInv2, WlDtInv2Args, wl_dtcwt_inv2_body)
 #undef WL_FUNCTOR
 
 // specialised tile kernels (wl_dtcwt_tile.h): float / half data and the reference's filter lengths only
-// output tiles of the level >= 2 DTCWT tile kernels (A/B builds override them)
+// output tiles of the level >= 2 DTCWT tile kernels
 #ifndef WL_INV2_TH
 #define WL_INV2_TH 16
 #define WL_INV2_TW 64
@@ -911,15 +911,10 @@ static int wl_afb_small_run(const WlAfbPyrReq& r) {
     a.lds_bytes = a.tap_off + 4 * L * 4;
     a.vec_ok = ((H * W) % 4 == 0) && ((int64_t)G * H * W * SZ) % 16 == 0 && (uintptr_t)r.x % 16 == 0;
     a.nblocks = (planes + G - 1) / G;                               // groups; a workgroup walks over several when the chip is full
-#ifndef WL_SMALL_WALK
-#define WL_SMALL_WALK 1          // 0: one workgroup per group (A/B builds)
-#endif
-    if (WL_SMALL_WALK) {
-        int per_cu = 160 * 1024 / a.lds_bytes;
-        if (per_cu > 8) per_cu = 8;
-        const int64_t resident = (int64_t)per_cu * wl_num_cus();
-        if (a.nblocks > resident) a.nblocks = resident;
-    }
+    int per_cu = 160 * 1024 / a.lds_bytes;
+    if (per_cu > 8) per_cu = 8;
+    const int64_t resident = (int64_t)per_cu * wl_num_cus();
+    if (a.nblocks > resident) a.nblocks = resident;
     switch (L) {
         case 2: return wl_afb_small_launch<T, 2>(a, r.stream);
         case 4: return wl_afb_small_launch<T, 4>(a, r.stream);

@@ -39,20 +39,6 @@ inline void wl_pk_fma_x_v(wl_v2& acc, wl_v2 tap, wl_v2 s) { wl_pk_fma_x(acc, tap
 inline void wl_pk_fma_y_v(wl_v2& acc, wl_v2 tap, wl_v2 s) { wl_pk_fma_y(acc, tap, s); }
 #endif
 
-#if defined(WL_DT12_TIME) && defined(__HIPCC__)
-#define WL_DT12_TICK() __builtin_readcyclecounter()
-#else
-#define WL_DT12_TICK() 0ull
-#endif
-// (timing builds: workgroup 0 leaves (total, barrier) kilocycles of one wave per role in ll2[16..21])
-#define WL_DT12_SYNC() { const unsigned long long t_ = WL_DT12_TICK(); ctx.sync(); tbar += WL_DT12_TICK() - t_; }
-#ifndef WL_DT12_ROWLOADS
-#define WL_DT12_ROWLOADS 0       // 1: the level-1 lanes read a row's samples when they filter it (fewer registers) instead of the four rows up front
-#endif
-#ifndef WL_DT12_ABLATE
-#define WL_DT12_ABLATE 0        // A/B builds: 1 = level-2 waves idle, 2 = no level-1 band-pass stores, 4 = no level-2 stores, 8 = no level-1 arithmetic
-#endif
-
 template <typename T>
 struct WlDtFusedArgs {
     WlDtFwd1Args<T> f;             // level 1: x, highs (ll = z = nullptr), taps, H = He, W = We (multiples of 4), ext = symmetric
@@ -124,7 +110,6 @@ struct WlDtFwd12Strip {
     // CU - and a lane reads a row's samples when it filters it, not the four rows of a half-batch up front)
     static const bool kLong = M > 4;
     static const int kMinWaves = kLong ? 2 : (MODE == 3 ? 4 : (kScat ? WL_DT12_MINW1 : (SW == 2 && MODE == 2 ? 5 : 6)));
-    static const bool kRowLoads = WL_DT12_ROWLOADS || kLong;
     static const int LW = (2 * M + 1 + 3) / 4 * 4;
     static const int PERIOD = LW / 4;
     static const int NS = 2 + 2 * M;
@@ -173,15 +158,6 @@ struct WlDtFwd12Strip {
         s.nhb1 = WARM1 + (s.g_hi - s.g_lo) + 2 * HG;
         s.nhb = (s.nhb1 + (MODE == 2 ? 1 : 0) + PF - 1) / PF * PF;
         return s;
-    }
-
-    static WL_DEV void report(const Args& a, const WlCtx& ctx, int lane, bool first, int slot, unsigned long long t0, unsigned long long tbar) {
-#if defined(WL_DT12_TIME) && defined(__HIPCC__)
-        if (MODE == 2 && ctx.bid == 0 && first && lane == 0) {
-            a.ll2[16 + slot] = (T)(float)((WL_DT12_TICK() - t0) >> 10);
-            a.ll2[17 + slot] = (T)(float)(tbar >> 10);
-        }
-#endif
     }
 
     // ---- stager wave: row `sidx` of every half-batch --------------------------------------------------------------------
@@ -256,8 +232,6 @@ struct WlDtFwd12Strip {
         // PF register sets: a row is requested PF - 1 .. PF half-batches before it is staged (measured: 2 .. 5 sets make no
         // difference - the loads are not what this kernel waits for).  The loads are unconditional (behind the last row: that
         // row again) and the loop has no branch, so that the compiler can count them and wait for exactly the oldest set.
-        unsigned long long tbar = 0;
-        const unsigned long long tstart = WL_DT12_TICK();
         RowRegs rr[PF];
 #pragma unroll
         for (int u = 0; u < PF; ++u) load(u < s.nhb1 ? u : s.nhb1 - 1, rr[u]);
@@ -266,11 +240,10 @@ struct WlDtFwd12Strip {
             for (int u = 0; u < PF; ++u) {
                 const int h = hb + u;
                 stage(h, rr[u]);                               // (behind level 1's last half-batch: into a slot nobody reads)
-                WL_DT12_SYNC();
+                ctx.sync();
                 load(h + PF < s.nhb1 ? h + PF : s.nhb1 - 1, rr[u]);
             }
         }
-        report(a, ctx, lane, sidx == 0, 4, tstart, tbar);
     }
 
     // ---- level-1 wave ---------------------------------------------------------------------------------------------------
@@ -427,21 +400,19 @@ struct WlDtFwd12Strip {
 #pragma unroll
         for (int t = 0; t < (kRot ? LW : 1); ++t) wc[t] = wl_v2{0.f, 0.f};
         char* const smem = ctx.smem;
-        unsigned long long tbar = 0;
-        const unsigned long long tstart = WL_DT12_TICK();
         for (int hb0 = 0; hb0 < s.nhb; hb0 += PERIOD) {
 #pragma unroll
             for (int ph = 0; ph < PERIOD; ++ph) {
                 const int hb = hb0 + ph;
                 if (hb >= s.nhb) break;
-                WL_DT12_SYNC();
-                if (!active || hb >= s.nhb1 || (WL_DT12_ABLATE & 8)) continue;
+                ctx.sync();
+                if (!active || hb >= s.nhb1) continue;
                 const char* slot = smem + a.st_off + (hb & 1) * 4 * a.st_pitch + soff;
                 char* l1slot = smem + a.l1_off + (hb & 1) * 4 * a.l1_pitch;
-                wl_v2 sr[kRowLoads ? 1 : 4][NC2];
-                if (!kRowLoads) {
+                wl_v2 sr[kLong ? 1 : 4][NC2];
+                if (!kLong) {
 #pragma unroll
-                    for (int i = 0; i < (kRowLoads ? 0 : 4); ++i)
+                    for (int i = 0; i < (kLong ? 0 : 4); ++i)
 #pragma unroll
                         for (int u = 0; u < NC2; ++u) {
                             const wl_f2 t = *reinterpret_cast<const wl_f2*>(slot + i * a.st_pitch + 8 * u);
@@ -455,16 +426,16 @@ struct WlDtFwd12Strip {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int w = (4 * ph + i) % LW;           // slot of the new input row e = o + M
-                    if (kRowLoads) {
+                    if (kLong) {
 #pragma unroll
                         for (int u = 0; u < NC2; ++u) {
                             const wl_f2 t = *reinterpret_cast<const wl_f2*>(slot + i * a.st_pitch + 8 * u);
                             sr[0][u] = wl_v2{t.x, t.y};
                         }
                     }
-                    wa[w] = row_filter<0>(R, sr[kRowLoads ? 0 : i]);
-                    wb[w] = row_filter<1>(R, sr[kRowLoads ? 0 : i]);
-                    if constexpr (kRot) wc[w] = row_filter_ba(R, sr[kRowLoads ? 0 : i]);
+                    wa[w] = row_filter<0>(R, sr[kLong ? 0 : i]);
+                    wb[w] = row_filter<1>(R, sr[kLong ? 0 : i]);
+                    if constexpr (kRot) wc[w] = row_filter_ba(R, sr[kLong ? 0 : i]);
                     wl_v2 aL, aH, bL, bH;
                     if (outp) {                                // (wave-uniform; such rows own no band-pass output)
                         col_filter_rev(R, wa, (w + LW - M) % LW, aL);
@@ -493,7 +464,7 @@ struct WlDtFwd12Strip {
                     if (!(i & 1)) { pL[0] = aL; pL[1] = bL; pH[0] = aH; pH[1] = bH; pC = cH; continue; }
                     // the quad (rows o - 1, o; columns 2q, 2q + 1) is complete: q2c of lh, hh, hl (reference
                     // transform_funcs.py:61-72: p = (upper left, upper right, lower left, lower right))
-                    if (!own || (WL_DT12_ABLATE & 2)) continue;
+                    if (!own) continue;
                     const float k = (float)WL_SQRT1_2;
                     const float lh0 = pH[0].x, lh1 = pH[1].x, lh2 = aH.x, lh3 = bH.x;
                     const float hh0 = kRot ? pC.x : pH[0].y, hh1 = kRot ? pC.y : pH[1].y, hh2 = kRot ? cH.x : aH.y, hh3 = kRot ? cH.y : bH.y;
@@ -537,7 +508,6 @@ struct WlDtFwd12Strip {
                 }
             }
         }
-        report(a, ctx, lane, cw == 0, 0, tstart, tbar);
     }
 
     // ---- level-2 wave ---------------------------------------------------------------------------------------------------
@@ -588,16 +558,14 @@ struct WlDtFwd12Strip {
         // the stagers fill it BEFORE barrier hb, level 2 reads it right after
         static const int LAG = MODE == 2 ? 1 : 0;
         const int G0 = s.o_base / 4 - LAG;                                     // LL1 group in the ring at half-batch hb: G0 + hb
-        unsigned long long tbar = 0;
-        const unsigned long long tstart = WL_DT12_TICK();
         static const int P2 = LQ / 2;
         for (int hb0 = 0; hb0 < s.nhb; hb0 += P2) {
 #pragma unroll
             for (int ph = 0; ph < P2; ++ph) {
                 const int hb = hb0 + ph;
                 if (hb >= s.nhb) break;
-                WL_DT12_SYNC();
-                if (hb < LAG || hb - LAG >= s.nhb1 || (WL_DT12_ABLATE & 1)) continue;
+                ctx.sync();
+                if (hb < LAG || hb - LAG >= s.nhb1) continue;
                 const int G = G0 + hb;
                 if (G < s.g_lo - HG) continue;                                 // rows of the level-1 warm-up
                 const char* l1slot = smem + a.l1_off + ((hb - LAG) & 1) * 4 * a.l1_pitch + l1lane;
@@ -626,7 +594,6 @@ struct WlDtFwd12Strip {
                     wl_pk_fma_x_v(xL0, tC[t], vE); wl_pk_fma_y_v(xH1, tC[t], vE);
                     wl_pk_fma_x_v(xL1, tC[t], vO); wl_pk_fma_y_v(xH0, tC[t], vO);
                 }
-                if ((WL_DT12_ABLATE & 4) && xL0.x != 12345.f) continue;
                 if (active && MODE != 5) {
                     Pair p0;
                     p0.a = (T)xL0.x; p0.b = (T)xL1.x;
@@ -681,7 +648,6 @@ struct WlDtFwd12Strip {
                 }
             }
         }
-        report(a, ctx, lane, qw == 0, 2, tstart, tbar);
     }
 
     static WL_DEV void run(const Args& a, const WlCtx& ctx) {

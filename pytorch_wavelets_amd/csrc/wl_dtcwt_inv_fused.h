@@ -77,10 +77,6 @@ struct WlDtInv21Strip {
     static_assert(ME == 4 && LW % 4 == 0, "level-1 pairs with M = 3 (7 / 5 taps): a segment starts one whole group above its rows");
     static const int PERIOD = LW / 4;                  // phases per rotation of the level-1 windows (4 rows per phase)
     static const int m2 = K2::m2, D2 = K2::D2;
-#ifndef WL_DTI21_KO
-#define WL_DTI21_KO 0      // knock-out experiments (tools/build_ab_dtinv.sh): bits switch parts of the work off - wrong results
-#endif
-    static const int KO = WL_DTI21_KO;
 #ifndef WL_DTI21_NG
 #define WL_DTI21_NG 4
 #endif
@@ -188,9 +184,6 @@ struct WlDtInv21Strip {
             src_quad_row(eq0 + hb, H2q, flip);
             char* sslot = ctx.smem + a.st2_off + (hb & 1) * 2 * a.st2_pitch;
             if (!qon) return;
-#if defined(__HIPCC__)
-            if (KO & 8) { asm volatile("" :: "v"(qd.l0), "v"(qd.l1), "v"(qd.b[0]), "v"(qd.b[1]), "v"(qd.b[2]), "v"(qd.b[3]), "v"(qd.b[4]), "v"(qd.b[5])); return; }
-#endif
             float re[6], im[6];
 #pragma unroll
             for (int o = 0; o < 6; ++o) { re[o] = (float)qd.b[o].x; im[o] = (float)qd.b[o].y; }
@@ -266,7 +259,7 @@ struct WlDtInv21Strip {
             for (int ph = 0; ph < m2; ++ph) {
                 const int hb = hb0 + ph;
                 if (hb >= s.n2) break;
-                if (active && !(KO & 4)) {
+                if (active) {
                     // row interpolation of both rows of the quad row
                     const char* slot = smem + a.st2_off + (hb & 1) * 2 * a.st2_pitch + soff;
 #pragma unroll
@@ -344,13 +337,8 @@ struct WlDtInv21Strip {
             for (int r = 0; r < 2; ++r) {
                 bool flip;
                 const int sq = src_quad_row(eq_first + 2 * h + r, H1q, flip);
-                if (KO & 32) {
 #pragma unroll
-                    for (int o = 0; o < 6; ++o) qd.b[r][o] = Pair2{(T)0.f, (T)0.f};
-                } else {
-#pragma unroll
-                    for (int o = 0; o < 6; ++o) qd.b[r][o] = *reinterpret_cast<const Pair2*>(hp + ((size_t)o * qplane + (size_t)sq * W1q) * 2);
-                }
+                for (int o = 0; o < 6; ++o) qd.b[r][o] = *reinterpret_cast<const Pair2*>(hp + ((size_t)o * qplane + (size_t)sq * W1q) * 2);
             }
         };
         const float k = (float)WL_SQRT1_2;
@@ -359,9 +347,6 @@ struct WlDtInv21Strip {
             if (!qon) return;
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
-#if defined(__HIPCC__)
-                if (KO & 2) { asm volatile("" :: "v"(qd.b[r][0]), "v"(qd.b[r][1]), "v"(qd.b[r][2]), "v"(qd.b[r][3]), "v"(qd.b[r][4]), "v"(qd.b[r][5])); continue; }
-#endif
                 bool flip;
                 const int sq = src_quad_row(eq_first + 2 * hb + r, H1q, flip);
                 const char* lrow = ctx.smem + a.l1_off + ((2 * sq) % (4 * NG)) * a.l1_pitch + lcol;
@@ -442,7 +427,7 @@ struct WlDtInv21Strip {
             for (int ph = 0; ph < PERIOD; ++ph) {
                 const int hb = hb0 + ph;
                 if (hb >= s.n1) break;
-                if (active && !(KO & 1)) {
+                if (active) {
                     const char* slot = smem + a.st1_off + (hb & 1) * 4 * a.st1_pitch + soff;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
@@ -455,7 +440,7 @@ struct WlDtInv21Strip {
                         const int o = e_first + 4 * hb + i - M;
                         float ya, yb;
                         K1::col_filter2(R, wa, wb, (w + LW - M) % LW, ya, yb);
-                        if (o >= s.r_lo && o < s.r_hi && (!(KO & 16) || ya == 12345.678f)) {
+                        if (o >= s.r_lo && o < s.r_hi) {
                             typedef T Vec2 __attribute__((ext_vector_type(2)));
                             Vec2 v = {(T)ya, (T)yb};
                             *reinterpret_cast<Vec2*>(yp + (unsigned)o * rowb + colb) = v;

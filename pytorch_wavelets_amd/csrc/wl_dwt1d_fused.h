@@ -19,9 +19,6 @@
 #include "wl_dwt_rows.h"   // wl_pk_fma_x / _y, wl_uniform_v2
 
 #define WL_DWT1D_MAXJ 4
-#ifndef WL_DWT1D_UNROLL
-#define WL_DWT1D_UNROLL 1      // output positions a thread works on at a time (A/B builds)
-#endif
 #ifndef WL_DWT1D_STAGES
 #define WL_DWT1D_STAGES 1      // chunks whose input samples are in flight (in registers) ahead of the one being computed
 #endif
@@ -195,9 +192,6 @@ struct WlDwt1dFused {
             // the inner levels hold positions inside the signal only: beyond its ends the extension rule picks the source
             const int in_lo = j == 0 ? g.clo[0] : 0, in_hi = j == 0 ? g.chi[0] : nj;
             const bool even = ((base - sorg) & 1) == 0;         // (uniform) the pairs (2k + base + 2u, + 1) are 8-byte aligned
-#if WL_DWT1D_UNROLL > 1
-#pragma unroll WL_DWT1D_UNROLL
-#endif
             for (int k = klo + tid; k < khi; k += kThreads) {
                 const int w0 = 2 * k + base;
                 wl_v2 acc0 = {0.f, 0.f}, acc1 = {0.f, 0.f};

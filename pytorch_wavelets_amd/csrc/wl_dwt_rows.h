@@ -39,16 +39,6 @@
 #define WL_ROWS_LOADERS 2       // loader waves: each issues the DMA of 4 / WL_ROWS_LOADERS rows of a half-batch (1, 2 or 4)
 #endif
 #define WL_ROWS_MAXHB 768       // half-batches one schedule table (kernel argument) can hold
-// WL_ROWS_ABLATE (tools/build_ab.sh builds only, never defined in the product): 1 = no global stores, 2 = no DMA
-// loads, 8 = in-kernel cycle counters written over a few LL samples
-#ifndef WL_ROWS_ABLATE
-#define WL_ROWS_ABLATE 0
-#endif
-#if (WL_ROWS_ABLATE & 8) && defined(__HIPCC__)
-#define WL_TICK() __builtin_readcyclecounter()
-#else
-#define WL_TICK() 0ull
-#endif
 #ifndef WL_ROWS_DEPTH
 #define WL_ROWS_DEPTH 3
 #endif
@@ -259,33 +249,23 @@ struct WlAfbRows {
 #pragma unroll
                 for (int p = 0; p < PPR; ++p) {
                     const int byte = (p * 64 + lane) * 16;
-                    if (!(WL_ROWS_ABLATE & 2)) wl_dma16(ctx, (unsigned)(slot + r * pitch + p * 1024), grow + byte, byte < row_bytes);
+                    wl_dma16(ctx, (unsigned)(slot + r * pitch + p * 1024), grow + byte, byte < row_bytes);
                 }
             }
         };
         for (int h = 0; h < D; ++h) issue(h);
-        unsigned long long tw = 0, tb = 0, ti = 0;
         for (int hb = 0; hb < sg.nhb; ++hb) {
-            const unsigned long long c0 = WL_TICK();
             if (hb < nhb0) {
-                if (!(WL_ROWS_ABLATE & 2)) wl_wait_vm<(D - 1) * NL>();   // the rows of this half-batch have landed
+                wl_wait_vm<(D - 1) * NL>();   // the rows of this half-batch have landed
                 char* slot = ctx.smem + ring + (hb % NSLOT) * 4 * pitch;
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
                     if (hdst[u] >= 0) *reinterpret_cast<T*>(slot + hdst[u]) = hsrc[u] < 0 ? (T)0 : *reinterpret_cast<const T*>(slot + hsrc[u]);
             }
-            const unsigned long long c1 = WL_TICK();
             ctx.sync();
-            const unsigned long long c2 = WL_TICK();
             if (hb < nhb0) issue(hb + D);                // its slot was consumed in half-batch hb-1
-            const unsigned long long c3 = WL_TICK();
-            tw += c1 - c0; tb += c2 - c1; ti += c3 - c2;
         }
         wl_wait_vm<0>();   // nothing may land after the workgroup has released its LDS
-        if ((WL_ROWS_ABLATE & 8) && lane == 0) {
-            T* o = a.ll + (size_t)plane * a.ll_ps;
-            o[8] = (T)(float)(tw >> 6); o[9] = (T)(float)(tb >> 6); o[10] = (T)(float)(ti >> 6);
-        }
     }
 
     // ---- compute waves of level j -----------------------------------------------------------------------------
@@ -422,14 +402,13 @@ struct WlAfbRows {
         const unsigned ob = L.ob;
         L.ob = ob + R.rowb;
         // keep: the row belongs to this segment (wave-uniform); halo rows of a cut plane are computed, not stored
-        const bool st = keep && (!(WL_ROWS_ABLATE & 1) || (cl.x + cl.y + ch.x + ch.y == 12345.f));
-        if (st) {
-            wl_store_stream(reinterpret_cast<T*>(R.hp0 + ob), (T)cl.y);    // W-lo / H-hi
-            wl_store_stream(reinterpret_cast<T*>(R.hp1 + ob), (T)ch.x);    // W-hi / H-lo
-            wl_store_stream(reinterpret_cast<T*>(R.hp2 + ob), (T)ch.y);    // W-hi / H-hi
+        if (keep) {
+            *reinterpret_cast<T*>(R.hp0 + ob) = (T)cl.y;    // W-lo / H-hi
+            *reinterpret_cast<T*>(R.hp1 + ob) = (T)ch.x;    // W-hi / H-lo
+            *reinterpret_cast<T*>(R.hp2 + ob) = (T)ch.y;    // W-hi / H-hi
         }
         if (LAST) {
-            if (st) *reinterpret_cast<T*>(R.llp + ((unsigned)orow * R.llrowb + R.kb)) = (T)cl.x;
+            if (keep) *reinterpret_cast<T*>(R.llp + ((unsigned)orow * R.llrowb + R.kb)) = (T)cl.x;
         } else {
             char* nrow = smem + (R.nring + (NP2 ? wl_uniform(wl_ring_slot(orow, R.rmask, R.nmagic)) : (orow & R.rmask)) * R.npitch);
             *reinterpret_cast<T*>(nrow + L.ndst) = (T)cl.x;
@@ -571,14 +550,9 @@ struct WlAfbRows {
 
         const int f0 = sg.f0[j], own_lo = sg.own_lo[j], own_hi = sg.own_hi[j];
         int fed = f0;           // next feed of this level (wave-uniform)
-        unsigned long long tb = 0, tf = 0, ts = 0, c3 = WL_TICK();
         for (int hb = 0; hb < sg.nhb; ++hb) {
-            const unsigned long long c0 = WL_TICK();
-            ts += c0 - c3;
             const int n = wl_uniform((int)(sg.sched[hb >> 2] >> (8 * (hb & 3) + 2 * j)) & 3);   // read before the barrier
             ctx.sync();
-            const unsigned long long c1 = WL_TICK();
-            tb += c1 - c0;
             const int orow = fed - WARM;   // the output row the next feed completes (once the window is full)
 #ifndef WL_ROWS_FEED2_MAXL
 #define WL_ROWS_FEED2_MAXL 10    // the longest filter that takes the two-feed form: at 12 taps its four sample rows spilled 15 VGPRs
@@ -601,19 +575,13 @@ struct WlAfbRows {
                     ++fed;
                 }
             }
-            c3 = WL_TICK();
-            tf += c3 - c1;
-        }
-        if ((WL_ROWS_ABLATE & 8) && j == 0 && k == 64) {   // second level-1 wave
-            T* o = a.ll + (size_t)plane * a.ll_ps;
-            o[0] = (T)(float)(tb >> 6); o[1] = (T)(float)(tf >> 6); o[2] = (T)(float)(ts >> 6);
         }
     }
 
     static WL_DEV void run(const Args& a, const WlCtx& ctx) {
         const int tid = ctx.tid;
         const int wave = wl_uniform(tid >> 6), lane = tid & 63;
-        if (a.guard) {   // "both axes filter with the same taps", checked against the taps as they are now (whatever tap count an A/B build arms)
+        if (a.guard) {   // "both axes filter with the same taps", checked against the taps as they are now
             const bool holds = a.lat ? *reinterpret_cast<const unsigned*>(a.lat) == WL_LAT_OK   // (WlTapPrep's verdict: same banks, mirror pair, lattice)
                                      : wl_taps_same(a.h_w_lo, a.h_h_lo, LT) && wl_taps_same(a.h_w_hi, a.h_h_hi, LT);
             if (!wl_guard_pass(a.guard, holds)) return;

@@ -3,11 +3,10 @@
 // periodization (rows and columns wrap), odd filter-bank offsets, float16 planes of any width, few planes.
 //
 // A workgroup owns one (plane, column strip, row segment) and marches down it once:
-//   * two STAGER waves bring every input row of the strip in by LDS-DMA (global_load_lds_dwordx4, 16-byte pieces, three
-//     half-batches ahead, counted waits) into a private ring in the input's own type.  A piece is a run of 16 bytes of
-//     the EXTENDED row: for the wrapping modes (periodic, periodization) the pieces beyond either end of the row simply
-//     come from the other end - a row is a whole number of pieces, so wrapping is per-piece address arithmetic, resolved
-//     once per lane - and a strip in the middle of the row gets its halo columns from its neighbours' columns;
+//   * the STAGER waves load every input row of the strip straight into registers, as 4-cell groups of the EXTENDED row
+//     one half-batch ahead (see stager_direct): for the wrapping modes (periodic, periodization) the groups beyond either
+//     end of the row simply come from the other end - wrapping is per-group address arithmetic, resolved once per lane -
+//     and a strip in the middle of the row gets its halo columns from its neighbours' columns;
 //   * the same waves then STAGE the rows they loaded: float32 copies (the float16 -> float32 conversion happens here,
 //     once per sample instead of once per tap) into a two-slot ring whose origin is chosen so that every compute lane
 //     reads its samples as whole, conflict-free 16-byte words; the mirrored cells of symmetric / reflect extension
@@ -37,26 +36,16 @@
 #define WL_STRIP_SWAVES 4       // stager waves: each loads and stages 4 / SWAVES of the 4 rows of a half-batch (one wave alone is
                                 // latency-bound: with two stagers the staging took longer than the arithmetic, with four it hides)
 #endif
-#ifndef WL_STRIP_ABLATE
-#define WL_STRIP_ABLATE 0       // measurement builds only (tools/build_ab_strip.sh): 1 = no arithmetic / stores in the compute
-#endif                          // waves, 2 = the stagers load but do not stage
-#ifndef WL_STRIP_DIRECT
-#define WL_STRIP_DIRECT 1        // stagers load straight into registers (0: through an LDS-DMA ring, the first version; A/B builds)
-#endif
 #ifndef WL_STRIP_PF
-#define WL_STRIP_PF 2           // register sets of a direct stager (rows in flight + the one being staged)
+#define WL_STRIP_PF 2           // register sets of a stager (rows in flight + the one being staged)
 #endif
 #ifndef WL_STRIP_D
-#define WL_STRIP_D 3            // half-batches of LDS-DMA in flight = slots of the DMA ring
+#define WL_STRIP_D 3            // half-batches of LDS-DMA in flight = slots of the DMA ring (the DTCWT strip kernel, wl_dtcwt_strip.h)
 #endif
-#if (WL_STRIP_ABLATE & 8) && defined(__HIPCC__)
-#define WL_STICK() __builtin_readcyclecounter()
-#else
-#define WL_STICK() 0ull
-#endif
-#define WL_STRIP_MAXPPR 5       // 1 KiB DMA instructions per row at most (strip rows of up to 5 KiB)
+#define WL_STRIP_MAXPPR 5       // 1 KiB DMA instructions per ring row at most (strip rows of up to 5 KiB): the DTCWT strip kernel's ring,
+                                // and a limit of the geometry the DWT strip launchers accept (wl_strip_api.inc)
 
-// One row, DMA ring -> staged float32 ring, by one stager wave (shared by the analysis and the synthesis strip kernels).
+// One row, DMA ring -> staged float32 ring, by one stager wave (the DTCWT strip kernel, wl_dtcwt_strip.h).
 template <typename T>
 struct WlStage {
     static const int SZ = (int)sizeof(T);
@@ -114,7 +103,8 @@ struct WlStripArgs {
     int H, W, Kh, Kw, ext, base;
     int nstrips, strip_cols;       // output columns per strip (even); the last strip may be narrower
     int nseg, seg_rows;            // output rows per segment; the last segment may be shorter
-    int dma_off, dma_pitch;        // DMA ring: WL_STRIP_D slots x 4 rows x dma_pitch bytes (input type)
+    int dma_off, dma_pitch;        // not read by the kernel (the ring of the retired LDS-DMA stagers; the fields keep the layout):
+                                   // dma_pitch = bytes of one ring row, which the launcher still bounds the accepted geometry with
     int st_off, st_pitch;          // staged ring: 2 slots x 4 rows x st_pitch bytes (float32)
     int lds_bytes;
     int pp, ring;                  // planes per workgroup (1, 2, 4: narrow strips, see run()) and the bytes of one plane's staged ring
@@ -156,7 +146,6 @@ struct WlAfbStrip {
     // half-batches after which the circular window is back where it started (lattice: the K delay slots, two feeds per half-batch)
     static const int PERIOD = LAT ? (KL % 2 ? KL : KL / 2) : LW / 4;
     static const int NV4 = (LT + 2 + 3) / 4;           // 16-byte words a lane reads per row: its L+2 samples
-    static const int D = WL_STRIP_D;
     static const bool kPipe = LT >= 14;    // see compute(): when the rows of a half-batch's second feed are requested
     static const int LROWS = 4 / WL_STRIP_SWAVES;
 
@@ -164,10 +153,10 @@ struct WlAfbStrip {
     struct Strip {
         int k0, k1;            // output columns [k0, k1)
         int e_lo;              // first extended column a lane reads = 2 k0 + base
-        int c0a;               // extended column of DMA-ring cell 0 (a multiple of A, <= e_lo)
-        int np;                // 16-byte pieces per DMA-ring row (up to the last one that is loaded)
-        int ppr;               // DMA instructions per row
-        int ng;                // 4-cell groups per DMA-ring row
+        int c0a;               // extended column of loaded cell 0 (a multiple of A, <= e_lo)
+        int np;                // 16-byte pieces per row (up to the last one that is loaded)
+        int ppr;               // np in 64-lane runs (the launcher's limits on the accepted geometry, inherited from the ring layout)
+        int ng;                // 4-cell groups per loaded row
         int dm;                // (e_lo - c0a) mod 4
         int lane_off;          // staged-ring byte offset of the first sample of output-column pair 0
         int o_lo, o_hi;        // output rows [o_lo, o_hi) of this segment
@@ -181,7 +170,7 @@ struct WlAfbStrip {
         s.e_lo = 2 * s.k0 + a.base;
         const int e_hi = 2 * (s.k1 - 1) + a.base + LT - 1 + 2;          // (+2: a lane always reads both its columns' samples)
         s.c0a = s.e_lo >= 0 ? s.e_lo / A * A : -((-s.e_lo + A - 1) / A * A);
-        int last = e_hi;                                                 // last extended column that arrives by DMA
+        int last = e_hi;                                                 // last extended column that is loaded
         if (!wraps(a.ext) && last > a.W - 1) last = a.W - 1;
         s.np = (last - s.c0a) / A + 1;
         s.ppr = (s.np + 63) / 64;
@@ -195,133 +184,12 @@ struct WlAfbStrip {
         s.nhb = (s.nfeeds + 1) / 2;
         return s;
     }
-    // staged-ring cell index of DMA-ring cell c (both along one row)
+    // staged-ring cell index of loaded cell c (both along one row)
     static WL_HD int staged_of(const Strip& s, int c) { return c + 4 - s.dm; }
 
-    // ---- stager wave --------------------------------------------------------------------------------------------
-    static WL_DEV void stager(const Args& a, const Strip& s, const WlCtx& ctx, int64_t plane, int lane, int sidx) {
-        const char* xp = reinterpret_cast<const char*>(a.x + (size_t)plane * a.x_ps);
-        const int row_stride = a.x_rs * SZ;
-        const bool wrap = wraps(a.ext);
-        const int We = a.W;                                   // (wrapping modes need an even W: the launcher checks)
-        const int e_first = a.base + 2 * s.o_lo;              // extended row of the segment's first feed
-        const int e_last = a.base + 2 * (s.o_lo + s.nfeeds) - 1;
-        const int rfirst = sidx * LROWS;
-        // per lane: source byte (inside a row) of its piece in each of the ppr DMA instructions of a row; -1 = off
-        int gbyte[WL_STRIP_MAXPPR];
-#pragma unroll
-        for (int q = 0; q < WL_STRIP_MAXPPR; ++q) {
-            const int p = q * 64 + lane;
-            int col = s.c0a + p * A;
-            bool on = q < s.ppr && p < s.np;
-            if (on && (unsigned)col >= (unsigned)a.W) {
-                if (wrap) col = wl_pmod(col, We); else on = false;
-            }
-            gbyte[q] = on ? col * SZ : -1;
-        }
-        // mirrored cells (symmetric / reflect, strips at either edge): item = (row r of my rows, cell); a lane handles
-        // items lane and lane + 64.  dst = staged cell, src = DMA-ring cell, both as byte offsets inside my rows' block.
-        int hdst[2], hsrc[2];
-        {
-            const int e_hi = 2 * (s.k1 - 1) + a.base + LT - 1 + 2;
-            const int nl = s.e_lo < 0 ? -s.e_lo : 0;                              // extended columns left of the row
-            const int nr = e_hi > a.W - 1 ? e_hi - (a.W - 1) : 0;                 // and right of it
-            const int NH = (a.ext == WL_EXT_SYM || a.ext == WL_EXT_REFL) ? nl + nr : 0;
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int it = lane + 64 * u;
-                hdst[u] = hsrc[u] = -1;
-                if (it < LROWS * NH) {
-                    const int r = it / NH, c = it - r * NH;
-                    const int e = c < nl ? s.e_lo + c : a.W + (c - nl);
-                    const int src = wl_ext(e, a.W, a.ext);
-                    hdst[u] = r * a.st_pitch + staged_of(s, e - s.c0a) * 4;
-                    hsrc[u] = r * a.dma_pitch + (src - s.c0a) * SZ;
-                }
-            }
-        }
-        auto issue = [&](int h) {
-            const int slot = a.dma_off + (h % D) * 4 * a.dma_pitch;
-#pragma unroll
-            for (int rr = 0; rr < LROWS; ++rr) {
-                const int r = rfirst + rr;
-                int e = e_first + 4 * h + r;
-                e = e < e_last ? e : e_last;
-                int src = e;
-                if ((unsigned)e >= (unsigned)a.H) {
-                    src = wl_ext(e, a.H, a.ext);
-                    src = src < 0 ? 0 : src;                  // zero rows: a dummy row keeps the DMA count exact
-                }
-                const char* grow = xp + (size_t)src * row_stride;
-#pragma unroll
-                for (int q = 0; q < WL_STRIP_MAXPPR; ++q)
-                    if (q < s.ppr) wl_dma16(ctx, (unsigned)(slot + r * a.dma_pitch + q * 1024), grow + gbyte[q], gbyte[q] >= 0);
-            }
-        };
-        const int nl_inst = LROWS * s.ppr;                    // DMA instructions per half-batch of this wave
-        // the 4-cell groups of a DMA-ring row that hold loaded data: [g_lo, g_hi); this lane owns groups lane + 64 i,
-        // i in [imin, imax)
-        const int ngl = (s.ng + 63) >> 6;
-        int imin, imax;
-        {
-            int g_lo = 0, g_hi = s.ng;
-            if (!wrap) {
-                if (s.c0a < 0) g_lo = (-s.c0a + 3) / 4;
-                const int lim = (a.W - s.c0a) / 4;            // (W and c0a are multiples of 4)
-                if (lim < g_hi) g_hi = lim;
-            }
-            imin = g_lo > lane ? (g_lo - lane + 63) / 64 : 0;
-            imax = g_hi > lane ? (g_hi - lane + 63) / 64 : 0;
-        }
-        for (int h = 0; h < D && h < s.nhb; ++h) issue(h);
-        int inflight = (D < s.nhb ? D : s.nhb);               // half-batches issued and not yet waited for
-        unsigned long long tw = 0, tg = 0, tb = 0, ti = 0;
-        for (int hb = 0; hb < s.nhb; ++hb) {
-            const unsigned long long c0 = WL_STICK();
-            wl_wait_vm_dyn((inflight - 1) * nl_inst);         // my rows of this half-batch have landed
-            --inflight;
-            const unsigned long long c1 = WL_STICK();
-            // stage my rows: DMA slot -> staged slot (float32, origin shifted so that lanes read aligned 16-byte words)
-            char* dslot = ctx.smem + a.dma_off + (hb % D) * 4 * a.dma_pitch + rfirst * a.dma_pitch;
-            char* sslot = ctx.smem + a.st_off + (hb & 1) * 4 * a.st_pitch + rfirst * a.st_pitch;
-            bool zrow[LROWS];
-#pragma unroll
-            for (int rr = 0; rr < LROWS; ++rr) {
-                int e = e_first + 4 * hb + rfirst + rr;
-                e = e < e_last ? e : e_last;
-                zrow[rr] = a.ext == WL_EXT_ZERO && (unsigned)e >= (unsigned)a.H;
-            }
-            // a lane stages the 4-cell groups lane, lane + 64, .. of each of its rows (see stage_row)
-            if (!(WL_STRIP_ABLATE & 2)) {
-#pragma unroll
-                for (int rr = 0; rr < LROWS; ++rr) {
-                    const char* srow = dslot + rr * a.dma_pitch + lane * 4 * SZ;
-                    char* drow = sslot + rr * a.st_pitch + lane * 16 + (4 - s.dm) * 4;
-                    if (zrow[rr]) WlStage<T>::template stage_row<4>(srow, drow, imin, imax, ngl);
-                    else if (s.dm == 0) WlStage<T>::template stage_row<0>(srow, drow, imin, imax, ngl);
-                    else if (s.dm == 2) WlStage<T>::template stage_row<2>(srow, drow, imin, imax, ngl);
-                    else WlStage<T>::template stage_row<1>(srow, drow, imin, imax, ngl);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-                if (hdst[u] >= 0) *reinterpret_cast<float*>(sslot + hdst[u]) = (float)*reinterpret_cast<const T*>(dslot + hsrc[u]);
-            const unsigned long long c2 = WL_STICK();
-            ctx.sync();
-            const unsigned long long c3 = WL_STICK();
-            if (hb + D < s.nhb) { issue(hb + D); ++inflight; }   // into the slot staged just now (nobody else reads it)
-            tw += c1 - c0; tg += c2 - c1; tb += c3 - c2; ti += WL_STICK() - c3;
-        }
-        wl_wait_vm<0>();
-        if ((WL_STRIP_ABLATE & 8) && lane == 0 && sidx == 0 && s.k0 == 0 && s.o_lo == 0) {
-            T* o = a.ll + (size_t)plane * a.ll_ps;
-            o[8] = (T)(float)(tw >> 10); o[9] = (T)(float)(tg >> 10); o[10] = (T)(float)(tb >> 10); o[11] = (T)(float)(ti >> 10);
-        }
-    }
-
-    // ---- stager wave, direct form: row `sidx` of every half-batch ------------------------------------------------------
+    // ---- stager wave: row `sidx` of every half-batch ------------------------------------------------------------------
     // The stager needs every sample in a register anyway (conversion, alignment): instead of LDS-DMA into a ring and an
-    // LDS read, the lane loads its 4-cell groups straight from global memory (8 / 16 bytes per lane, consecutive lanes on
+    // LDS read (the first version of this kernel), the lane loads its 4-cell groups straight from global memory (8 / 16 bytes per lane, consecutive lanes on
     // consecutive addresses, wrapped columns resolved once per lane) one half-batch ahead, into one of two register
     // sets, and stages the other.  No DMA ring in LDS, no counted waits (the compiler tracks ordinary loads), no DMA
     // instruction issue - which cost a stager ~250 cycles apiece under load.
@@ -429,19 +297,17 @@ struct WlAfbStrip {
             }
         };
         auto stage = [&](int hb, const RowRegs (&rr)[PP * LROWS]) {
-            if (!(WL_STRIP_ABLATE & 2)) {
 #pragma unroll
-                for (int q = 0; q < PP * LROWS; ++q) {
-                    const bool zero = src_row(hb, q % LROWS) < 0;
-                    char* srow0 = ctx.smem + a.st_off + (q / LROWS) * a.ring + ((hb & 1) * 4 + sidx * LROWS + q % LROWS) * a.st_pitch;
-                    char* drow = srow0 + lane * 16 + (4 - s.dm) * 4;
-                    if (s.dm == 0) stage_regs<0, NGL>(rr[q], drow, imin, imax, zero);
-                    else if (s.dm == 2) stage_regs<2, NGL>(rr[q], drow, imin, imax, zero);
-                    else stage_regs<1, NGL>(rr[q], drow, imin, imax, zero);
+            for (int q = 0; q < PP * LROWS; ++q) {
+                const bool zero = src_row(hb, q % LROWS) < 0;
+                char* srow0 = ctx.smem + a.st_off + (q / LROWS) * a.ring + ((hb & 1) * 4 + sidx * LROWS + q % LROWS) * a.st_pitch;
+                char* drow = srow0 + lane * 16 + (4 - s.dm) * 4;
+                if (s.dm == 0) stage_regs<0, NGL>(rr[q], drow, imin, imax, zero);
+                else if (s.dm == 2) stage_regs<2, NGL>(rr[q], drow, imin, imax, zero);
+                else stage_regs<1, NGL>(rr[q], drow, imin, imax, zero);
 #pragma unroll
-                    for (int u = 0; u < 2; ++u)
-                        if (hdst[u] >= 0) *reinterpret_cast<float*>(srow0 + hdst[u]) = zero ? 0.f : (float)rr[q].h[u];
-                }
+                for (int u = 0; u < 2; ++u)
+                    if (hdst[u] >= 0) *reinterpret_cast<float*>(srow0 + hdst[u]) = zero ? 0.f : (float)rr[q].h[u];
             }
         };
         // PF register sets: the rows of the next PF - 1 half-batches are in flight while one is staged.  Measured on config 5
@@ -622,20 +488,16 @@ struct WlAfbStrip {
         for (int t = 0; t < KL; ++t) SA[t] = SB[t] = wl_v2{0.f, 0.f};
         char* const smem = ctx.smem;
         int fed = 0;                                                          // feeds done (wave-uniform)
-        unsigned long long tbar = 0, tmath = 0;
         for (int hb0 = 0; hb0 < s.nhb; hb0 += PERIOD) {
 #pragma unroll
             for (int ph = 0; ph < PERIOD; ++ph) {
                 const int hb = hb0 + ph;
                 if (hb >= s.nhb) break;
-                const unsigned long long c0 = WL_STICK();
                 ctx.sync();
-                const unsigned long long c1 = WL_STICK();
-                tbar += c1 - c0;
                 const int left = s.nfeeds - fed;
                 const int n = left > 2 ? 2 : left;
                 const char* slot = smem + a.st_off + sub * a.ring + (hb & 1) * 4 * a.st_pitch + soff;
-                if (active && !(WL_STRIP_ABLATE & 1)) {
+                if (active) {
                     // Short filters: all four rows of the half-batch are requested from LDS before the first FMA.  From 14
                     // taps on the registers do not allow that at four waves per SIMD: the rows of the second feed are
                     // requested behind the row filter of the first and land during its column filter.
@@ -667,20 +529,18 @@ struct WlAfbStrip {
                                     col_pass(R, wa, first, cla, cha);
                                     col_pass(R, wb, first, clb, chb);
                                 }
-                                if (!(WL_STRIP_ABLATE & 4) || cla.x + clb.y + cha.x + chb.y == 1.2345e30f) {
-                                    // (the second feed's row is one further down when the first feed emitted one too)
-                                    const unsigned k = (i == 1 && fed >= WARM) ? 1u : 0u;
-                                    char* const q0 = pll + (size_t)(k * R.llrowb);
-                                    char* const q1 = ph0 + (size_t)(k * R.rowb);
-                                    char* const q2 = ph1 + (size_t)(k * R.rowb);
-                                    char* const q3 = ph2 + (size_t)(k * R.rowb);
-                                    if (R.pair_ok) {          // (one branch per row, not one per store)
-                                        wl_store2_s(q0, voff, cla.x, clb.x, (T*)nullptr); wl_store2_s(q1, voff, cla.y, clb.y, (T*)nullptr);
-                                        wl_store2_s(q2, voff, cha.x, chb.x, (T*)nullptr); wl_store2_s(q3, voff, cha.y, chb.y, (T*)nullptr);
-                                    } else {
-                                        store_single(R, q0 + voff, cla.x, clb.x); store_single(R, q1 + voff, cla.y, clb.y);
-                                        store_single(R, q2 + voff, cha.x, chb.x); store_single(R, q3 + voff, cha.y, chb.y);
-                                    }
+                                // (the second feed's row is one further down when the first feed emitted one too)
+                                const unsigned k = (i == 1 && fed >= WARM) ? 1u : 0u;
+                                char* const q0 = pll + (size_t)(k * R.llrowb);
+                                char* const q1 = ph0 + (size_t)(k * R.rowb);
+                                char* const q2 = ph1 + (size_t)(k * R.rowb);
+                                char* const q3 = ph2 + (size_t)(k * R.rowb);
+                                if (R.pair_ok) {          // (one branch per row, not one per store)
+                                    wl_store2_s(q0, voff, cla.x, clb.x, (T*)nullptr); wl_store2_s(q1, voff, cla.y, clb.y, (T*)nullptr);
+                                    wl_store2_s(q2, voff, cha.x, chb.x, (T*)nullptr); wl_store2_s(q3, voff, cha.y, chb.y, (T*)nullptr);
+                                } else {
+                                    store_single(R, q0 + voff, cla.x, clb.x); store_single(R, q1 + voff, cla.y, clb.y);
+                                    store_single(R, q2 + voff, cha.x, chb.x); store_single(R, q3 + voff, cha.y, chb.y);
                                 }
                             }
                         }
@@ -693,12 +553,7 @@ struct WlAfbStrip {
                     ph1 += (size_t)((unsigned)em * R.rowb); ph2 += (size_t)((unsigned)em * R.rowb);
                 }
                 fed += n;
-                tmath += WL_STICK() - c1;
             }
-        }
-        if ((WL_STRIP_ABLATE & 8) && lane == 0 && cw == 0 && sub == 0 && s.k0 == 0 && s.o_lo == 0) {
-            T* o = a.ll + (size_t)plane * a.ll_ps;
-            o[0] = (T)(float)(tbar >> 10); o[1] = (T)(float)(tmath >> 10);
         }
     }
 
@@ -735,29 +590,27 @@ struct WlAfbStrip {
             __builtin_amdgcn_s_setprio(2);   // every compute wave waits for the stagers at the barrier
 #endif
             const int sidx = wave - WL_STRIP_CWAVES;
-            if (WL_STRIP_DIRECT) {
-                const int ngl = (s.ng + 63) >> 6;
-                if constexpr (LROWS == 1) {   // (several planes: four stager waves, one row of each plane per wave)
-                    if (a.pp == 4) {          // (the launcher: ngl <= 2 with four planes, <= 3 with two)
-                        if (ngl == 1) stager_direct<1, 4>(a, s, ctx, plane, lane, sidx); else stager_direct<2, 4>(a, s, ctx, plane, lane, sidx);
-                        return;
-                    }
-                    if (a.pp == 2) {
-                        if (ngl == 1) stager_direct<1, 2>(a, s, ctx, plane, lane, sidx);
-                        else if (ngl == 2) stager_direct<2, 2>(a, s, ctx, plane, lane, sidx);
-                        else stager_direct<3, 2>(a, s, ctx, plane, lane, sidx);
-                        return;
-                    }
+            const int ngl = (s.ng + 63) >> 6;
+            if constexpr (LROWS == 1) {   // (several planes: four stager waves, one row of each plane per wave)
+                if (a.pp == 4) {          // (the launcher: ngl <= 2 with four planes, <= 3 with two)
+                    if (ngl == 1) stager_direct<1, 4>(a, s, ctx, plane, lane, sidx); else stager_direct<2, 4>(a, s, ctx, plane, lane, sidx);
+                    return;
                 }
-                switch (ngl) {
-                    case 1: stager_direct<1, 1>(a, s, ctx, plane, lane, sidx); break;
-                    case 2: stager_direct<2, 1>(a, s, ctx, plane, lane, sidx); break;
-                    case 3: stager_direct<3, 1>(a, s, ctx, plane, lane, sidx); break;
-                    case 4: stager_direct<4, 1>(a, s, ctx, plane, lane, sidx); break;
-                    case 5: stager_direct<5, 1>(a, s, ctx, plane, lane, sidx); break;
-                    default: stager_direct<6, 1>(a, s, ctx, plane, lane, sidx); break;
+                if (a.pp == 2) {
+                    if (ngl == 1) stager_direct<1, 2>(a, s, ctx, plane, lane, sidx);
+                    else if (ngl == 2) stager_direct<2, 2>(a, s, ctx, plane, lane, sidx);
+                    else stager_direct<3, 2>(a, s, ctx, plane, lane, sidx);
+                    return;
                 }
-            } else stager(a, s, ctx, plane, lane, sidx);
+            }
+            switch (ngl) {
+                case 1: stager_direct<1, 1>(a, s, ctx, plane, lane, sidx); break;
+                case 2: stager_direct<2, 1>(a, s, ctx, plane, lane, sidx); break;
+                case 3: stager_direct<3, 1>(a, s, ctx, plane, lane, sidx); break;
+                case 4: stager_direct<4, 1>(a, s, ctx, plane, lane, sidx); break;
+                case 5: stager_direct<5, 1>(a, s, ctx, plane, lane, sidx); break;
+                default: stager_direct<6, 1>(a, s, ctx, plane, lane, sidx); break;
+            }
             return;
         }
         const int nact = WL_STRIP_CWAVES / a.pp;              // compute waves per plane

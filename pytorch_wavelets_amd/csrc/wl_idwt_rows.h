@@ -27,9 +27,12 @@
 #define WL_IROWS_MAXLEV 3
 #define WL_IROWS_WAVES 14
 #define WL_IROWS_MAXHB 640
+// WL_IROWS_ABLATE & 8 (timing builds only, never defined in the product): WlSfbRows::compute leaves per-wave cycle counters
+// (barrier, feed) in row 0 of x.  The last of the measurement switches: taking these accumulators out changes the register
+// allocation of two kernels of this unit, so they go in a change of their own, with its own measurement.
 #ifndef WL_IROWS_ABLATE
-#define WL_IROWS_ABLATE 0       // measurement builds only (tools/build_ab.sh): 1 no global stores, 2 no DMA, 4 no arithmetic,
-#endif                          // 8 per-wave cycle counters into row 0 of x, 64 a barrier in every other half-batch only
+#define WL_IROWS_ABLATE 0
+#endif
 #if (WL_IROWS_ABLATE & 8) && defined(__HIPCC__)
 #define WL_ITICK() __builtin_readcyclecounter()
 #else
@@ -181,16 +184,14 @@ struct WlSfbRows {
             // the ring bytes it overwrites held rows of the previous revolution: all of them consumed, and not in the
             // half-batch that is running now (rows >= fed - 2)
             if (r != r0 && cend > (fed - 2 - (r - 1) * R) * rb) return false;
-            if (!(WL_IROWS_ABLATE & 2)) {
-                const bool whole = pbyte + 16 <= plane_bytes;                 // at least lane 0 has a whole piece
-                const bool on = rbyte + lane * 16 < ring_bytes && pbyte + lane * 16 + 16 <= plane_bytes;
-                const bool tail = ptail && p16 >= pbyte && p16 < pbyte + (cend - rbyte);   // the plane's last dwords are in this step
+            const bool whole = pbyte + 16 <= plane_bytes;                 // at least lane 0 has a whole piece
+            const bool on = rbyte + lane * 16 < ring_bytes && pbyte + lane * 16 + 16 <= plane_bytes;
+            const bool tail = ptail && p16 >= pbyte && p16 < pbyte + (cend - rbyte);   // the plane's last dwords are in this step
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (i >= ns) break;
-                    if (whole) wl_dma16_s(ctx, (unsigned)(dst[i] + rbyte), src[i], (unsigned)(pbyte + lane * 16), on);
-                    if (tail) wl_dma4_s(ctx, (unsigned)(dst[i] + rbyte + (p16 - pbyte)), src[i], (unsigned)(p16 + lane * 4), lane < ptail);
-                }
+            for (int i = 0; i < 4; ++i) {
+                if (i >= ns) break;
+                if (whole) wl_dma16_s(ctx, (unsigned)(dst[i] + rbyte), src[i], (unsigned)(pbyte + lane * 16), on);
+                if (tail) wl_dma4_s(ctx, (unsigned)(dst[i] + rbyte + (p16 - pbyte)), src[i], (unsigned)(p16 + lane * 4), lane < ptail);
             }
             ++issued;
             rbyte += WL_IROWS_CHUNK; pbyte += WL_IROWS_CHUNK;
@@ -198,30 +199,21 @@ struct WlSfbRows {
             return true;
         };
         while (try_issue()) {}
-        unsigned long long tw = 0, tb = 0, ti = 0;
         unsigned word = sg.sched[0];
         for (int hb = 0; hb < sg.nhb; ++hb) {
-            const unsigned long long c0 = WL_ITICK();
             const int n = (int)(word >> (8 * (hb & 3) + 2 * j)) & 3;
             if ((hb & 3) == 3) word = sg.sched[(hb >> 2) + 1 < WL_IROWS_MAXHB / 4 ? (hb >> 2) + 1 : 0];
             if (n) {   // the steps under rows fed .. fed+n-1 have landed
                 const int nd = need(fed + n - 1);
                 if (issued < nd) wl_fail();   // the launcher's geometry checks rule this out
-                if (!(WL_IROWS_ABLATE & 2)) wl_wait_vm_dyn((issued - nd) * ns);
+                wl_wait_vm_dyn((issued - nd) * ns);
                 landed = nd;
             }
-            const unsigned long long c1 = WL_ITICK();
-            if (!(WL_IROWS_ABLATE & 64) || !(hb & 1)) ctx.sync();
-            const unsigned long long c2 = WL_ITICK();
+            ctx.sync();
             fed += n;
             while (try_issue()) {}
-            tw += c1 - c0; tb += c2 - c1; ti += WL_ITICK() - c2;
         }
         wl_wait_vm<0>();   // nothing may land after the workgroup has released its LDS
-        if ((WL_IROWS_ABLATE & 8) && lane == 0) {
-            T* o = a.y + (size_t)plane * a.g[0].OH * a.g[0].OW + 4 * (ctx.tid >> 6);
-            o[0] = (T)(float)(tw >> 6); o[1] = (T)(float)(tb >> 6); o[2] = (T)(float)(ti >> 6);
-        }
     }
 
     // ---- loader wave, periodization: one coefficient ROW of every source per step, into ring rows with the wrapped cells in front ------
@@ -262,12 +254,10 @@ struct WlSfbRows {
                 sr = sr >= Kh ? sr - Kh : sr;
                 const unsigned gro = (unsigned)sr * (unsigned)rowb + (unsigned)lo;
                 const unsigned slot = (unsigned)((next & (R - 1)) * P);
-                if (!(WL_IROWS_ABLATE & 2)) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        if (i >= ns) break;
-                        wl_dma16_s(ctx, (unsigned)dst[i] + slot, src[i], gro, lon);
-                    }
+                for (int i = 0; i < 4; ++i) {
+                    if (i >= ns) break;
+                    wl_dma16_s(ctx, (unsigned)dst[i] + slot, src[i], gro, lon);
                 }
                 next += G;
                 return true;
@@ -277,16 +267,14 @@ struct WlSfbRows {
             sr = sr >= Kh ? sr - Kh : sr;
             const unsigned gro = (unsigned)sr * (unsigned)rowb;
             const unsigned slot = (unsigned)((next & (R - 1)) * P + g.per_d0);
-            if (!(WL_IROWS_ABLATE & 2)) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (i >= ns) break;
-                    for (int q = 0; q < nseg; ++q) {
-                        const int byte = (q * 64 + lane) * 16;
-                        wl_dma16_s(ctx, (unsigned)dst[i] + slot + (unsigned)(q * WL_IROWS_CHUNK), src[i], gro + (unsigned)byte, byte + 16 <= rowb);
-                    }
-                    if (tail) wl_dma4_s(ctx, (unsigned)dst[i] + slot + (unsigned)rowb16, src[i], gro + (unsigned)(rowb16 + lane * 4), lane < tail);
+            for (int i = 0; i < 4; ++i) {
+                if (i >= ns) break;
+                for (int q = 0; q < nseg; ++q) {
+                    const int byte = (q * 64 + lane) * 16;
+                    wl_dma16_s(ctx, (unsigned)dst[i] + slot + (unsigned)(q * WL_IROWS_CHUNK), src[i], gro + (unsigned)byte, byte + 16 <= rowb);
                 }
+                if (tail) wl_dma4_s(ctx, (unsigned)dst[i] + slot + (unsigned)rowb16, src[i], gro + (unsigned)(rowb16 + lane * 4), lane < tail);
             }
             ++next;
             return true;
@@ -299,7 +287,7 @@ struct WlSfbRows {
             if (n) {   // rows fed .. fed+n-1 have landed; their wrapped cells: copies of the row's last WARM coefficients
                 const int nd = (fed + n + G - 1) & ~(G - 1);   // (whole groups)
                 if (next < nd) wl_fail();   // the launcher's geometry checks rule this out
-                if (!(WL_IROWS_ABLATE & 2)) wl_wait_vm_dyn(G > 1 ? ((next - nd) / G) * per_step : (next - nd) * per_step);
+                wl_wait_vm_dyn(G > 1 ? ((next - nd) / G) * per_step : (next - nd) * per_step);
                 landed = nd;
                 if (WARM > 0) {
                     for (int it = lane; it < n * ns * WARM; it += 64) {
@@ -424,7 +412,6 @@ struct WlSfbRows {
     template <int j>
     static WL_DEV void emit_per(const Wave& R, char* smem, int m, wl_v2 y0, wl_v2 y1) {
         if (j == 0) {
-            if ((WL_IROWS_ABLATE & 1) && y0.x + y0.y + y1.x + y1.y != 1.2345e30f) return;
             int r0 = m + R.rot2;
             r0 = r0 < 0 ? r0 + R.xoh : r0;
             r0 = r0 >= R.xoh ? r0 - R.xoh : r0;
@@ -467,20 +454,12 @@ struct WlSfbRows {
         if (j == 0) {
             // every row a level-0 feed produces is one this segment owns: its feeds start at own_lo / 2 and end with the
             // feed that makes row own_hi - 1
-            if ((WL_IROWS_ABLATE & 1) && y0.x + y0.y + y1.x + y1.y != 1.2345e30f) return;   // keeps the arithmetic alive
             char* r0 = R.yp + ((unsigned)m * R.yrowb + R.ycol);
             char* r1 = r0 + R.yrowb;
             if (!R.odd_wave) {
-#if (WL_STREAM_NT & 2) && defined(__HIPCC__)
-                typedef T WlVec2 __attribute__((ext_vector_type(2), aligned(sizeof(T))));
-                WlVec2 v = {(T)y0.x, (T)y1.x}, w = {(T)y0.y, (T)y1.y};
-                __builtin_nontemporal_store(v, reinterpret_cast<WlVec2*>(r0));
-                __builtin_nontemporal_store(w, reinterpret_cast<WlVec2*>(r1));
-#else
                 T v[2] = {(T)y0.x, (T)y1.x}, w[2] = {(T)y0.y, (T)y1.y};
                 *reinterpret_cast<WlPairT*>(r0) = *reinterpret_cast<WlPairT*>(v);
                 *reinterpret_cast<WlPairT*>(r1) = *reinterpret_cast<WlPairT*>(w);
-#endif
             } else {   // the wave that holds the last pair of an odd-width row: that lane has one column only
                 *reinterpret_cast<T*>(r0) = (T)y0.x;
                 *reinterpret_cast<T*>(r1) = (T)y0.y;
@@ -565,13 +544,13 @@ struct WlSfbRows {
             const int n = (int)(word >> (8 * (hb & 3) + 2 * j)) & 3;
             if ((hb & 3) == 3) word = sg.sched[(hb >> 2) + 1 < WL_IROWS_MAXHB / 4 ? (hb >> 2) + 1 : 0];
             const unsigned long long c0 = WL_ITICK();
-            if (!(WL_IROWS_ABLATE & 64) || !(hb & 1)) ctx.sync();
+            ctx.sync();
             const unsigned long long c1 = WL_ITICK();
             tf += c0 - c2; tb += c1 - c0; c2 = c1;
             if (n == 0) continue;
             const int k = fed;
             fed += n;
-            if (!active || (WL_IROWS_ABLATE & 4)) continue;
+            if (!active) continue;
             const int m = 2 * (k - WARM);
             wl_v2 y0, y1;
             if constexpr (LAT != 0) {                    // (every feed: the lattice's state; its first K - 1 outputs of a segment are the warm-up)
@@ -636,6 +615,6 @@ struct WlSfbRows {
         else if (lev == 1) compute<1>(a, sg, ctx, plane, arg, lane, soff);
         else if (lev == 2) compute<2>(a, sg, ctx, plane, arg, lane, soff);
         else
-            for (int hb = 0; hb < sg.nhb; ++hb) if (!(WL_IROWS_ABLATE & 64) || !(hb & 1)) ctx.sync();   // spare wave: keeps the barrier count
+            for (int hb = 0; hb < sg.nhb; ++hb) ctx.sync();   // spare wave: keeps the barrier count
     }
 };

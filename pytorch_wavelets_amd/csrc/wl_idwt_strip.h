@@ -3,9 +3,9 @@
 // output is rolled by L/2-1), 14 to 20 taps, planes wider than one workgroup, float16 planes of any width.
 //
 // A workgroup owns one (plane, strip of output columns, segment of output rows) and marches down it once:
-//   * four STAGER waves, one per source (ll, lh, hl, hh), bring the coefficient rows of the strip in by LDS-DMA (16-byte
-//     pieces of the EXTENDED row: under periodization the pieces beyond either end come from the other end), three
-//     half-batches ahead, and copy what they loaded as float32 (the float16 -> float32 conversion happens once per
+//   * four STAGER waves, one per source (ll, lh, hl, hh), load the coefficient rows of the strip straight into registers
+//     (4-cell groups of the EXTENDED row: under periodization the groups beyond either end come from the other end), one
+//     half-batch ahead, and copy what they loaded as float32 (the float16 -> float32 conversion happens once per
 //     coefficient) into a two-slot ring laid out so that every compute lane reads aligned 8-byte words;
 //   * a compute lane owns FOUR adjacent output columns = two polyphase column pairs.  Per coefficient row ("feed") it
 //     reads its L/2+1 (+1) coefficients of each source, runs the polyphase row synthesis of both pairs,
@@ -24,7 +24,7 @@
 #pragma once
 #include "wl_common.h"
 #include "wl_dwt_rows.h"   // wl_pk_fma_x / _y, wl_pk_mul_x / _y, wl_uniform_v2
-#include "wl_dwt_strip.h"  // WlStage, WL_STRIP_* geometry constants
+#include "wl_dwt_strip.h"  // WL_STRIP_* geometry constants
 #include "wl_lattice.h"
 
 template <typename T>
@@ -43,7 +43,8 @@ struct WlIStripArgs {
     int nstrips, strip_units;      // lane units (4 output columns each) per strip; the last strip may be narrower
     int nseg, seg_pairs;           // z-row pairs per segment
     int m_first, m_end;            // z-row pairs [m_first, m_end) that hold output rows
-    int dma_off, dma_pitch;        // DMA ring: WL_STRIP_D slots x 8 rows (4 sources x 2 coefficient rows) x dma_pitch bytes
+    int dma_off, dma_pitch;        // not read by the kernel (the ring of the retired LDS-DMA stagers; the fields keep the layout):
+                                   // dma_pitch = bytes of one ring row, which the launcher still bounds the accepted geometry with
     int st_off, st_pitch;          // staged ring: 2 slots x 8 rows x st_pitch bytes (float32)
     int lds_bytes;
     int pp, ring;                  // planes per workgroup (1, 2, 4: narrow strips, see WlAfbStrip::run) and the bytes of one plane's staged ring
@@ -79,13 +80,13 @@ struct WlSfbStrip {
     static const int NC2 = (NT + 1 + 1) / 2;   // 8-byte words a lane reads per source row: its NT + 1 coefficients
     static const int LW = (HL + 1) / 2 * 2;    // window slots: a multiple of the 2 rows of a half-batch
     static const int PERIOD = LAT ? (HL % 2 ? HL : HL / 2) : LW / 2;   // (lattice: HL delay slots, two feeds per half-batch)
-    static const int D = WL_STRIP_D;
 
     struct Strip {
         int u0, u1;            // lane units [u0, u1): output columns [4 u0, 4 u1)
         int q_lo;              // first coefficient column a lane reads
-        int c0a;               // coefficient column of DMA-ring cell 0 (a multiple of A, <= q_lo)
-        int np, ppr, ng;       // pieces / DMA instructions / 4-cell groups per DMA-ring row
+        int c0a;               // coefficient column of loaded cell 0 (a multiple of A, <= q_lo)
+        int np, ppr, ng;       // 16-byte pieces / 64-lane runs of pieces / 4-cell groups per loaded row (np, ppr: the launcher's limits
+                               // on the accepted geometry, inherited from the ring layout)
         int dm;                // (q_lo - c0a) & 1
         int lane_off;          // staged-ring byte offset of lane unit u0's first coefficient
         int m_lo, m_hi;        // z-row pairs of this segment
@@ -107,7 +108,7 @@ struct WlSfbStrip {
         s.ng = s.np * A / 4;
         const int d = s.q_lo - s.c0a;
         s.dm = d & 1;
-        s.lane_off = (d + s.dm) * 4;                 // staged cell of DMA cell c = c + dm: lanes read 8-byte aligned
+        s.lane_off = (d + s.dm) * 4;                 // staged cell of loaded cell c = c + dm: lanes read 8-byte aligned
         s.m_lo = a.m_first + seg * a.seg_pairs;
         s.m_hi = s.m_lo + a.seg_pairs < a.m_end ? s.m_lo + a.seg_pairs : a.m_end;
         s.e_first = s.m_lo - (HL - 1);
@@ -116,71 +117,8 @@ struct WlSfbStrip {
         return s;
     }
 
-    // ---- stager wave: source b (0 = ll, 1..3 = the high-pass bands) ---------------------------------------------------
-    static WL_DEV void stager(const Args& a, const Strip& s, const WlCtx& ctx, int64_t plane, int lane, int b) {
-        const char* bp = b == 0 ? reinterpret_cast<const char*>(a.ll + (size_t)plane * a.ll_ps)
-                                : reinterpret_cast<const char*>(a.highs + ((size_t)plane * 3 + (b - 1)) * ((size_t)a.Kh * a.Kw));
-        const int row_stride = (b == 0 ? a.ll_rs : a.Kw) * SZ;
-        const int e_last = s.e_first + s.nfeeds - 1;
-        int gbyte[WL_STRIP_MAXPPR];
-#pragma unroll
-        for (int q = 0; q < WL_STRIP_MAXPPR; ++q) {
-            const int p = q * 64 + lane;
-            int col = s.c0a + p * A;
-            bool on = q < s.ppr && p < s.np;
-            if (on && (unsigned)col >= (unsigned)a.Kw) {
-                if (a.per) col = wl_pmod(col, a.Kw); else on = false;
-            }
-            gbyte[q] = on ? col * SZ : -1;
-        }
-        const int ngl = (s.ng + 63) >> 6;
-        int imin, imax;
-        {
-            int g_lo = 0, g_hi = s.ng;
-            if (!a.per) {
-                if (s.c0a < 0) g_lo = (-s.c0a + 3) / 4;
-                const int lim = (a.Kw - s.c0a) / 4;
-                if (lim < g_hi) g_hi = lim;
-            }
-            imin = g_lo > lane ? (g_lo - lane + 63) / 64 : 0;
-            imax = g_hi > lane ? (g_hi - lane + 63) / 64 : 0;
-        }
-        auto issue = [&](int h) {
-            const int slot = a.dma_off + (h % D) * 8 * a.dma_pitch;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                int e = s.e_first + 2 * h + i;
-                e = e < e_last ? e : e_last;
-                const int r = a.per ? wl_pmod(e, a.Kh) : e;      // (non-periodization: every feed is a real row)
-                const char* grow = bp + (size_t)r * row_stride;
-#pragma unroll
-                for (int q = 0; q < WL_STRIP_MAXPPR; ++q)
-                    if (q < s.ppr) wl_dma16(ctx, (unsigned)(slot + (2 * b + i) * a.dma_pitch + q * 1024), grow + gbyte[q], gbyte[q] >= 0);
-            }
-        };
-        const int nl_inst = 2 * s.ppr;
-        for (int h = 0; h < D && h < s.nhb; ++h) issue(h);
-        int inflight = D < s.nhb ? D : s.nhb;
-        for (int hb = 0; hb < s.nhb; ++hb) {
-            wl_wait_vm_dyn((inflight - 1) * nl_inst);
-            --inflight;
-            const char* dslot = ctx.smem + a.dma_off + (hb % D) * 8 * a.dma_pitch + 2 * b * a.dma_pitch;
-            char* sslot = ctx.smem + a.st_off + (hb & 1) * 8 * a.st_pitch + 2 * b * a.st_pitch;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const char* srow = dslot + i * a.dma_pitch + lane * 4 * SZ;
-                char* drow = sslot + i * a.st_pitch + lane * 16 + s.dm * 4;
-                if (s.dm == 0) WlStage<T>::template stage_row<0>(srow, drow, imin, imax, ngl);
-                else WlStage<T>::template stage_row<1>(srow, drow, imin, imax, ngl);
-            }
-            ctx.sync();
-            if (hb + D < s.nhb) { issue(hb + D); ++inflight; }
-        }
-        wl_wait_vm<0>();
-    }
-
-    // ---- stager wave, direct form (see wl_dwt_strip.h): source b, two coefficient rows per half-batch, loaded straight
-    // into registers one half-batch ahead; NGL = 4-cell groups per lane and row (compile-time: static load counts)
+    // ---- stager wave (see wl_dwt_strip.h): source b (0 = ll, 1..3 = the high-pass bands), two coefficient rows per half-batch,
+    // loaded straight into registers one half-batch ahead; NGL = 4-cell groups per lane and row (compile-time: static load counts)
     static const int MAXG = 6;
     typedef T Quad4 __attribute__((ext_vector_type(4), aligned(sizeof(T)), may_alias));   // element-aligned: any row width / pitch
     template <int NGL> struct RowRegs { Quad4 g[2][NGL]; T t[2]; };
@@ -550,22 +488,20 @@ struct WlSfbStrip {
             __builtin_amdgcn_s_setprio(2);
 #endif
             const int b = wave - WL_STRIP_CWAVES;
-            if (WL_STRIP_DIRECT) {
-                const int ngl = (s.ng + 63) >> 6;
-                // (the launcher: ngl = 1 with four planes, <= 2 with two - what strips of one / two compute waves need; a wave holds
-                // 2 rows x ngl x pp groups x WL_STRIP_PF sets in registers, 128 of them at <2, 4> in float32)
-                if (a.pp == 4) stager_direct<1, 4>(a, s, ctx, plane, lane, b);
-                else if (a.pp == 2) {
-                    if (ngl == 1) stager_direct<1, 2>(a, s, ctx, plane, lane, b); else stager_direct<2, 2>(a, s, ctx, plane, lane, b);
-                } else switch (ngl) {
-                    case 1: stager_direct<1, 1>(a, s, ctx, plane, lane, b); break;
-                    case 2: stager_direct<2, 1>(a, s, ctx, plane, lane, b); break;
-                    case 3: stager_direct<3, 1>(a, s, ctx, plane, lane, b); break;
-                    case 4: stager_direct<4, 1>(a, s, ctx, plane, lane, b); break;
-                    case 5: stager_direct<5, 1>(a, s, ctx, plane, lane, b); break;
-                    default: stager_direct<6, 1>(a, s, ctx, plane, lane, b); break;
-                }
-            } else stager(a, s, ctx, plane, lane, b);
+            const int ngl = (s.ng + 63) >> 6;
+            // (the launcher: ngl = 1 with four planes, <= 2 with two - what strips of one / two compute waves need; a wave holds
+            // 2 rows x ngl x pp groups x WL_STRIP_PF sets in registers, 128 of them at <2, 4> in float32)
+            if (a.pp == 4) stager_direct<1, 4>(a, s, ctx, plane, lane, b);
+            else if (a.pp == 2) {
+                if (ngl == 1) stager_direct<1, 2>(a, s, ctx, plane, lane, b); else stager_direct<2, 2>(a, s, ctx, plane, lane, b);
+            } else switch (ngl) {
+                case 1: stager_direct<1, 1>(a, s, ctx, plane, lane, b); break;
+                case 2: stager_direct<2, 1>(a, s, ctx, plane, lane, b); break;
+                case 3: stager_direct<3, 1>(a, s, ctx, plane, lane, b); break;
+                case 4: stager_direct<4, 1>(a, s, ctx, plane, lane, b); break;
+                case 5: stager_direct<5, 1>(a, s, ctx, plane, lane, b); break;
+                default: stager_direct<6, 1>(a, s, ctx, plane, lane, b); break;
+            }
             return;
         }
         const int nact = WL_STRIP_CWAVES / a.pp;              // compute waves per plane

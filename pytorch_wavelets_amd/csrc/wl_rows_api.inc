@@ -15,11 +15,7 @@
 // are bound by what a SIMD issues: 128x3x256^2 as 384 workgroups of two half planes ran 0.045 ms against 0.041, 128x3x224^2 as 256
 // of three 0.029 against 0.035; three levels with 384 workgroups 0.049 against 0.045), the synthesis kernel two (128x3x224^2 J = 2 as
 // 384 workgroups 0.064 against 0.080 ms; J = 1 as 256: 0.030 against 0.064): tools/gpu_r5w.py, same box.
-#ifndef WL_ROWS_PACK_CUT
-#define WL_ROWS_PACK_CUT 1
-#endif
 static int wl_rows_pack_and_cut(int64_t planes, int pp_cap, int lds_plane, int rows, int halo, int64_t cost_now, int64_t max_wgs) {
-    if (!WL_ROWS_PACK_CUT) return 0;
     const int64_t cus = wl_num_cus(), slots = 2 * cus;
     int p2 = pp_cap < planes ? pp_cap : (int)planes;
     // (workgroups for three quarters of the CUs at least: half planes of a packed unit still beat whole planes on every CU)

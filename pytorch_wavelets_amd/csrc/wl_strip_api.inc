@@ -18,17 +18,14 @@
 // launches; the workgroups of a partly filled last round run faster, so rounds count fractionally above one.)
 // Planes per workgroup of a one-level DWT strip kernel (K::run): `nact` = compute waves one plane's strip keeps busy, `rows` = the
 // rows row segments are cut from, `ngl_max` >= 4-cell groups per stager lane and row (the stager holds pp x that many in registers:
-// <= lim2 with two planes, <= lim4 with four - the instantiations the kernel has).  More than one only when the strip is the whole row, the direct stagers are compiled in
-// and the chip still gets a workgroup for every slot.
-#ifndef WL_STRIP_PP
-#define WL_STRIP_PP 1           // 0: one plane per workgroup always (A/B builds)
-#endif
+// <= lim2 with two planes, <= lim4 with four - the instantiations the kernel has).  More than one only when the strip is the whole row, the
+// workgroup has its four compute and four stager waves and the chip still gets a workgroup for every slot.
 #ifndef WL_STRIP_MINSEG
 #define WL_STRIP_MINSEG 32      // shortest row segment of the one-level DWT strip kernels.  A workgroup's cadence is one half-batch per
 #endif                          // ~3000 cycles whatever else the chip does: a small level (config 5's fourth: 512 planes of 256 x 256) is
                                 // over soonest with MANY short workgroups - four planes each, four segments of 32 rows - not few long ones
 static int wl_strip_planes_per_wg(int nact, int nstrips, int64_t planes, int rows, int ngl_max, int st_off, int ring, int lim2, int lim4) {
-    if (!WL_STRIP_PP || !WL_STRIP_DIRECT || WL_STRIP_CWAVES != 4 || WL_STRIP_SWAVES != 4 || nstrips != 1) return 1;
+    if (WL_STRIP_CWAVES != 4 || WL_STRIP_SWAVES != 4 || nstrips != 1) return 1;
     int pp = nact == 1 ? 4 : nact == 2 ? 2 : 1;
     int maxseg = rows / WL_STRIP_MINSEG;
     maxseg = maxseg < 1 ? 1 : maxseg;
@@ -37,7 +34,7 @@ static int wl_strip_planes_per_wg(int nact, int nstrips, int64_t planes, int row
 }
 
 #ifndef WL_STRIP_WGS
-#define WL_STRIP_WGS 2     // workgroups per CU the one-level DWT strip kernels are cut for (A/B builds)
+#define WL_STRIP_WGS 2     // workgroups per CU the one-level DWT strip kernels are cut for
 #endif
 static void wl_pick_segments(int rows, int64_t units, int wgs_per_cu, int halo, int align, int* seg_rows, int* nseg,
                              int min_rows = 64, bool partial = false) {
@@ -54,12 +51,6 @@ static void wl_pick_segments(int rows, int64_t units, int wgs_per_cu, int halo, 
         if (partial) cost = (units * ns > slots ? units * ns : slots) * (sr + halo + 8);   // (the same scale: x slots)
         if (best < 0 || cost < best) { best = cost; *seg_rows = sr; *nseg = ns; }
     }
-#ifdef WL_SEG_PROBE
-    if (const char* e = getenv("WL_SEG_N")) {
-        const int n = atoi(e);
-        if (n >= 1 && rows / n >= 16) { *seg_rows = wl_align_up(wl_cdiv(rows, n), align); *nseg = wl_cdiv(rows, *seg_rows); }
-    }
-#endif
 }
 
 // Round 6: THREE translation units (WL_STRIP_PARTS: bit 0 = the analysis strip kernels, wl_strip_hip.hip; bit 1 = the synthesis strip kernels,
@@ -85,9 +76,8 @@ static int wl_afb_strip_launch(const WlAfbReq& r, const float* lat, int guard = 
     a.Kh = wl_coeff_len(H, LT, r.mode); a.Kw = wl_coeff_len(W, LT, r.mode);
     a.base = wl_afb_base(W, LT, r.mode);
     // the stagers load 4-cell groups at element alignment: any row width and pitch; wrapped groups (periodic /
-    // periodization) must be whole groups.  (The LDS-DMA form of the A/B builds needs 16-byte rows and pitches.)
+    // periodization) must be whole groups.
     if (K::wraps(a.ext) && W % 4) return WL_ERR_UNSUPPORTED;
-    if (!WL_STRIP_DIRECT && ((W * SZ) % 16 || (uintptr_t)r.x % 16 || ((int64_t)x_rs * SZ) % 16 || (x_ps * SZ) % 16)) return WL_ERR_UNSUPPORTED;
     if ((uintptr_t)r.x % SZ) return WL_ERR_UNSUPPORTED;
     if ((int64_t)H * x_rs >= (1LL << 29) || (int64_t)a.Kh * a.Kw >= (1LL << 29) || (int64_t)a.Kh * ll_rs >= (1LL << 29)) return WL_ERR_UNSUPPORTED;
     if (W < 2 * LT || H < 2) return WL_ERR_UNSUPPORTED;       // a mirrored / wrapped halo must come from inside the row, once
@@ -105,12 +95,12 @@ static int wl_afb_strip_launch(const WlAfbReq& r, const float* lat, int guard = 
         const int np = (2 * a.strip_cols + LT + 1 + 2 * A) / A + 1;              // pieces per row, worst alignment
         const int ng = np * A / 4;
         ng_worst = ng;
-        a.dma_pitch = wl_align_up(np * 16, 16);
+        a.dma_pitch = wl_align_up(np * 16, 16);                   // (host only: the bytes of a row as 16-byte pieces, bounded below)
         a.st_pitch = wl_align_up((4 * ng + 8 + 4 * K::NV4) * 4, 16);
         a.dma_off = 0;
-        a.st_off = WL_STRIP_DIRECT ? 0 : K::D * 4 * a.dma_pitch;   // (the direct stagers have no DMA ring)
+        a.st_off = 0;                                              // (the staged ring is all of the LDS)
         a.lds_bytes = a.st_off + 2 * 4 * a.st_pitch;
-        if (wl_cdiv(np, 64) <= WL_STRIP_MAXPPR && a.lds_bytes <= 80 * 1024 && (!WL_STRIP_DIRECT || wl_cdiv(ng, 64) <= K::MAXG)) break;
+        if (wl_cdiv(np, 64) <= WL_STRIP_MAXPPR && a.lds_bytes <= 80 * 1024 && wl_cdiv(ng, 64) <= K::MAXG) break;
     }
     // a narrow level (one strip that needs two / one of the four compute waves): two / four planes per workgroup (K::run) when
     // that still leaves workgroups for every slot of the chip
@@ -119,7 +109,9 @@ static int wl_afb_strip_launch(const WlAfbReq& r, const float* lat, int guard = 
     a.lds_bytes = a.st_off + a.pp * a.ring;
     // row segments (two workgroups of 8 waves per CU)
     wl_pick_segments(a.Kh, wl_cdiv64(planes, a.pp) * a.nstrips, WL_STRIP_WGS, K::WARM, 1, &a.seg_rows, &a.nseg, WL_STRIP_MINSEG);
-    // every strip must find its mirrored halo inside the columns it loads, and issue no empty DMA instruction
+    // every strip must find its mirrored halo inside the columns it loads; the limits on np / ppr / dma_pitch and the "no run of 64
+    // pieces that lies outside the row" loop below are limits of the accepted geometry inherited from the layout of the retired DMA
+    // ring (rows of at most WL_STRIP_MAXPPR KiB as 16-byte pieces): they decide which shapes this kernel takes
     for (int st = 0; st < a.nstrips; ++st) {
         const typename K::Strip s = K::geometry(a, st, 0);
         if (s.np < 1 || s.ppr > WL_STRIP_MAXPPR || s.np * 16 > a.dma_pitch) return WL_ERR_UNSUPPORTED;
@@ -137,8 +129,8 @@ static int wl_afb_strip_launch(const WlAfbReq& r, const float* lat, int guard = 
             const int nl = s.e_lo < 0 ? -s.e_lo : 0, nr = e_hi > W - 1 ? e_hi - (W - 1) : 0;
             if (K::LROWS * (nl + nr) > 128) return WL_ERR_UNSUPPORTED;
         }
-        // the first piece of every DMA instruction of a row must be a piece that is loaded (a wave-instruction whose
-        // lanes are all off would not count): pieces 0, 64, 128, .. lie left of the row only in the first instruction
+        // every run of 64 pieces of a row must hold a piece that is loaded (inherited from the ring layout, where such a run was one
+        // DMA instruction): pieces 0, 64, 128, .. lie left of the row only in the first run
         for (int q = 0; q < s.ppr; ++q) {
             bool any = false;
             for (int l = 0; l < 64 && !any; ++l) {
@@ -258,9 +250,8 @@ static int wl_sfb_strip_launch(const WlSfbReq& r, const float* lat, int guard = 
     a.sh = a.sw;
     if ((a.sw & 1) != SODD) return WL_ERR_UNSUPPORTED;
     // the stagers load 4-cell groups at element alignment: any row width and pitch; wrapped groups (periodization) must be
-    // whole groups.  (The LDS-DMA form of the A/B builds needs 16-byte rows and pitches.)
+    // whole groups.
     if (a.per && Kw % 4) return WL_ERR_UNSUPPORTED;
-    if (!WL_STRIP_DIRECT && ((Kw * SZ) % 16 || (uintptr_t)r.ll % 16 || (uintptr_t)r.highs % 16 || ((int64_t)ll_rs * SZ) % 16 || (ll_ps * SZ) % 16)) return WL_ERR_UNSUPPORTED;
     if ((uintptr_t)r.ll % SZ || (uintptr_t)r.highs % SZ) return WL_ERR_UNSUPPORTED;
     if ((int64_t)Kh * Kw >= (1LL << 28) || (int64_t)OH * OW >= (1LL << 29) || (int64_t)Kh * ll_rs >= (1LL << 29)) return WL_ERR_UNSUPPORTED;
     if (Kw < LT || Kh < HL) return WL_ERR_UNSUPPORTED;
@@ -279,25 +270,27 @@ static int wl_sfb_strip_launch(const WlSfbReq& r, const float* lat, int guard = 
         const int np = (2 * a.strip_units + K::NT + 1 + 2 * A) / A + 1;
         const int ng = np * A / 4;
         ng_worst = ng;
-        a.dma_pitch = np * 16;
+        a.dma_pitch = np * 16;                                     // (host only: the bytes of a row as 16-byte pieces, bounded below)
         a.st_pitch = wl_align_up((4 * ng + 2 + A + 2 * K::NC2) * 4, 16);
         a.dma_off = 0;
-        a.st_off = WL_STRIP_DIRECT ? 0 : K::D * 8 * a.dma_pitch;   // (the direct stagers have no DMA ring)
+        a.st_off = 0;                                              // (the staged ring is all of the LDS)
         a.lds_bytes = a.st_off + 2 * 8 * a.st_pitch;
-        if (wl_cdiv(np, 64) <= WL_STRIP_MAXPPR && a.lds_bytes <= 80 * 1024 && (!WL_STRIP_DIRECT || wl_cdiv(ng, 64) <= K::MAXG)) break;
+        if (wl_cdiv(np, 64) <= WL_STRIP_MAXPPR && a.lds_bytes <= 80 * 1024 && wl_cdiv(ng, 64) <= K::MAXG) break;
     }
     // a narrow level: two / four planes per workgroup (WlAfbStrip::run) when that still leaves workgroups for every slot of the chip
     a.ring = 2 * 8 * a.st_pitch;
     a.pp = wl_strip_planes_per_wg(wl_cdiv(units, 64), a.nstrips, planes, a.m_end - a.m_first, wl_cdiv(ng_worst, 64), a.st_off, a.ring, 2, 1);
     a.lds_bytes = a.st_off + a.pp * a.ring;
     wl_pick_segments(a.m_end - a.m_first, wl_cdiv64(planes, a.pp) * a.nstrips, WL_STRIP_WGS, HL - 1, 1, &a.seg_pairs, &a.nseg, WL_STRIP_MINSEG);
+    // (np / ppr / dma_pitch and the loop over runs of 64 pieces: limits of the accepted geometry inherited from the layout of the retired
+    // DMA ring, as in wl_afb_strip_launch)
     for (int st = 0; st < a.nstrips; ++st) {
         const typename K::Strip s = K::geometry(a, st, 0);
         if (s.np < 1 || s.ppr > WL_STRIP_MAXPPR || s.np * 16 > a.dma_pitch) return WL_ERR_UNSUPPORTED;
         if ((4 * s.ng + s.dm) * 4 > a.st_pitch) return WL_ERR_UNSUPPORTED;
         if (s.lane_off + 8 * (s.u1 - s.u0 - 1) + 8 * K::NC2 > a.st_pitch) return WL_ERR_UNSUPPORTED;
         if (!a.per && s.q_lo < 0) return WL_ERR_UNSUPPORTED;
-        for (int q = 0; q < s.ppr; ++q) {     // no DMA instruction whose lanes are all off
+        for (int q = 0; q < s.ppr; ++q) {     // no run of 64 pieces that lies outside the row
             bool any = false;
             for (int l = 0; l < 64 && !any; ++l) {
                 const int p = q * 64 + l;

@@ -1,5 +1,7 @@
 """Row segments of the lean level-1 / level-2 kernels (A/B build with -DWL_SEG_PROBE; WL_SEG_N forces the number of segments):
-the three launches of ScatLayerj2 on 64x3x256x256 and the ScatLayer of config 4."""
+the three launches of ScatLayerj2 on 64x3x256x256 and the ScatLayer of config 4.
+Kept as the source of the figures DESIGN.md quotes.  The WL_SEG_PROBE hook of wl_pick_segments is gone from the library: WL_SEG_N
+no longer has any effect, and the script now only times the launcher's own segment counts."""
 import os, sys, json, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench, pytorch_wavelets_amd as pw

@@ -1,3 +1,5 @@
+# Kept as the source of the figures DESIGN.md quotes.  It needs a library built with -DWL_SEG_PROBE (ab/libwl_segprobe.so), a hook of
+# wl_pick_segments that is gone from the library: WL_SEG_N no longer has any effect and every row of the sweep would be the same.
 python -m pytest tests/test_dtcwt_gpu.py tests/test_ext_gpu.py -q -m gpu 2>&1 | tail -1
 python tools/gpu_scatj2_time.py 2>&1 | head -2
 export WL_LIB=ab/libwl_segprobe.so
