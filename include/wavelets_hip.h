@@ -49,7 +49,8 @@ extern "C" {
  *          must be recompiled against this header (check wl_version() >= 210).
  *   220 (this header): dtype WL_BF16 (bfloat16 data, float taps) everywhere WL_F16 is accepted; no argument list changes.
  *          Later under 220, new names only: wl_dwt3d_depth_analysis / wl_dwt3d_depth_synthesis (the depth axis of the 3-D DWT;
- *          a caller that needs them looks the symbols up); wl_dtcwt1d_analysis / wl_dtcwt1d_synthesis (the 1-D DTCWT) likewise. */
+ *          a caller that needs them looks the symbols up); wl_dtcwt1d_analysis / wl_dtcwt1d_synthesis (the 1-D DTCWT) and
+ *          wl_wpt2d_analysis / wl_wpt2d_synthesis (the 2-D wavelet packet level) likewise. */
 int wl_version(void);
 const char* wl_backend(void);
 
@@ -493,6 +494,33 @@ int wl_dwt3d_depth_synthesis(const void* const* lo, const int64_t* lo_outer_stri
                              void* const* y, const int64_t* y_outer_stride, const int64_t* y_axis_stride, int nsrc, int dtype,
                              int64_t outer, int K, int64_t inner, int ny, const void* g0, int L0, const void* g1, int L1,
                              int mode, int chunks, void* stream);
+
+/* One level of the 2-D wavelet PACKET transform on packed band blocks (csrc/wl_wpt2d.h): x (planes, H, W) through a plane stride
+ * and a row pitch (elements, rows unit-stride) -> y (planes, 4, Kh, Kw) dense, Kh / Kw = wl_dwt_coeff_len, band s = 2 b_W + b_H
+ * (b = 1: highpass; 0 = ll, 1 = W-lo/H-hi, 2 = W-hi/H-lo, 3 = hh): the ll and the three highs of wl_dwt2d_analysis side by side,
+ * so that the next level reads y as (4 planes, Kh, Kw) without a copy.  Taps: the stored (reversed) float taps of
+ * wl_dwt2d_analysis, h_w_* along W, h_h_* along H, L of each; the five modes of wl_dwt2d_analysis.  A workgroup owns a tile of at
+ * most 512 coefficients per band of one plane or, for planes of at most 256 coefficients, of a run of consecutive planes.
+ * float32 / float16 / bfloat16, even L <= 20.
+ * nlev: levels per launch, 1 or 2.  nlev = 2: y (planes, 16, H/4, W/4), band 4 s1 + s2 (level 1 the high digit), the level-1 bands
+ * kept in LDS (a tile of 8 x 16 coefficients of each of the 16 bands per workgroup) - periodization only, H and W multiples of 4,
+ * L <= 12, H/2 and W/2 >= L - 1; anything else returns WL_ERR_UNSUPPORTED and the caller goes level by level.
+ * Returns WL_ERR_UNSUPPORTED also for float64, odd L, L > 20, nlev > 2, the generic_only option, periodization of a plane shorter
+ * than the filter (H + (H & 1) < L - 1, likewise W: the reference folds the wrapped tail once), planes of 2^29 elements and more
+ * and grids beyond 2^31 - 1 workgroups: callers then run wl_dwt2d_analysis_strided and copy the four bands. */
+int wl_wpt2d_analysis(const void* x, int64_t x_plane_stride, int x_row_stride, void* y, int dtype, int64_t planes, int H, int W,
+                      int nlev, const void* h_w_lo, const void* h_w_hi, const void* h_h_lo, const void* h_h_hi, int L, int mode,
+                      void* stream);
+
+/* The matching synthesis level: y (planes, 4, Kh, Kw) dense -> x_out (planes, OH, OW) dense, wl_dwt2d_synthesis's rule with all
+ * four bands read from the packed block; OH <= 2 Kh - L + 2 (periodization: 2 Kh), likewise OW - smaller sizes crop (the backward
+ * of the analysis level).  nlev = 2: y (planes, 16, Kh, Kw) -> x_out (planes, 4 Kh, 4 Kw) in the envelope above (OH = 4 Kh, OW = 4 Kw,
+ * 2 Kh and 2 Kw >= L - 1).  Returns WL_ERR_UNSUPPORTED for float64, odd L, L > 20, generic_only, nlev > 2,
+ * periodization with fewer outputs than taps (2 Kh < L - 2, likewise Kw) and band planes of 2^29 elements and more: callers
+ * then run wl_dwt2d_synthesis on the band slices. */
+int wl_wpt2d_synthesis(const void* y, void* x_out, int dtype, int64_t planes, int Kh, int Kw, int OH, int OW, int nlev,
+                       const void* g_w_lo, const void* g_w_hi, const void* g_h_lo, const void* g_h_hi, int L, int mode,
+                       void* stream);
 
 #ifdef __cplusplus
 }

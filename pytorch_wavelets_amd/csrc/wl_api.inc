@@ -17,6 +17,7 @@
 #include "wl_swt2d.h"
 #include "wl_iswt2d.h"
 #include "wl_dwt3d.h"
+#include "wl_wpt2d.h"
 #include "wl_dtcwt_kernels.h"
 #include "wl_dtcwt_tile.h"
 #include "wl_dtcwt_rot.h"
@@ -1179,3 +1180,4 @@ extern "C" int wl_synth1d(const void* lo, const void* hi, void* y, int dtype, in
 }
 
 #include "wl_dwt3d_api.inc"
+#include "wl_wpt2d_api.inc"

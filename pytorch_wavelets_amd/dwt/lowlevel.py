@@ -854,6 +854,132 @@ def sfb2d(ll, lh, hl, hh, filts, mode='zero'):
     return SFB2D.apply(ll, highs, g0_row, g1_row, g0_col, g1_col, mode_to_int(mode))
 
 
+# ---- the 2-D wavelet packet transform: every sub-band is split again (csrc/wl_wpt2d.h) ---------------------------------
+# A level takes (N, C, H, W) to the packed block (N, C, 4, Kh, Kw), band s = 2 b_W + b_H = AFB2D's (low, highs) side by side; the
+# next level reads it as (N, 4C, Kh, Kw) - a view - so the band index of a J-level tree is the base-4 number of its path, level 1
+# first.
+def _wpt_analysis(x, banks, mode, nlev=1):
+    """`nlev` (1 or 2) packet analysis levels, banks = (h0_row, h1_row, h0_col, h1_col) as AFB2D takes them.  One level: one launch
+    of the packed-band kernel, or - where it declines - ops.afb2d with the four bands copied into the packed tensor.  Two levels:
+    one launch of the two-level kernel where ops.WPT_FUSED allows and the launcher takes it, else level by level."""
+    if nlev == 2:
+        y = ops.wpt2d_afb(x, banks[0], banks[1], banks[2], banks[3], mode, nlev=2) if ops.WPT_FUSED else None
+        if y is None:
+            N, C = x.shape[:2]
+            y = _wpt_analysis(x, banks, mode)
+            y = _wpt_analysis(y.view(N, 4 * C, y.shape[-2], y.shape[-1]), banks, mode)
+            y = y.view(N, C, 16, y.shape[-2], y.shape[-1])
+        return y
+    y = ops.wpt2d_afb(x, banks[0], banks[1], banks[2], banks[3], mode)
+    if y is None:
+        ll, highs = ops.afb2d(x, banks[0], banks[1], banks[2], banks[3], mode)
+        y = torch.empty(tuple(ll.shape[:2]) + (4,) + tuple(ll.shape[2:]), dtype=ll.dtype, device=ll.device)
+        y[:, :, 0].copy_(ll)
+        y[:, :, 1:].copy_(highs)
+    return y
+
+
+def _wpt_synthesis(y, banks, mode, out_hw=None, nlev=1):
+    """`nlev` (1 or 2) packet synthesis levels of y (N, C, 4**nlev, Kh, Kw), the result cropped to out_hw if given (two levels: the
+    level in between to the size whose analysis out_hw has): the mirror image of _wpt_analysis, ops.sfb2d on the bands sliced
+    out of the packed tensor where a one-level launch declines."""
+    if y.dim() != 5 or y.shape[2] != 4 ** nlev:
+        raise ValueError('%d packet level(s) take (N, C, %d, H, W) coefficients, not %s' % (nlev, 4 ** nlev, tuple(y.shape)))
+    if nlev == 2:
+        x = ops.wpt2d_sfb(y, banks[0], banks[1], banks[2], banks[3], mode, out_hw=out_hw, nlev=2) if ops.WPT_FUSED else None
+        if x is None:
+            N, C = y.shape[:2]
+            mid = None
+            if out_hw is not None:
+                mid = (ops.coeff_len(out_hw[0], banks[2].numel(), mode), ops.coeff_len(out_hw[1], banks[0].numel(), mode))
+            x = _wpt_synthesis(y.reshape(N, 4 * C, 4, y.shape[-2], y.shape[-1]), banks, mode, out_hw=mid)
+            x = _wpt_synthesis(x.view(N, C, 4, x.shape[-2], x.shape[-1]), banks, mode, out_hw=out_hw)
+        return x
+    x = ops.wpt2d_sfb(y, banks[0], banks[1], banks[2], banks[3], mode, out_hw=out_hw)
+    if x is None:
+        x = ops.sfb2d(y[:, :, 0], y[:, :, 1:], banks[0], banks[1], banks[2], banks[3], mode, out_hw=out_hw)
+    return x
+
+
+class AFBWPT2D(Function):
+    """One or two levels of 2-D packet analysis.  ``AFBWPT2D.apply(x, h0_row, h1_row, h0_col, h1_col, mode_int, nlev) ->
+    y (N,C,4**nlev,H',W')``; one level = AFB2D's (low, highs) as one packed block.  Backward = the packet synthesis with the same
+    stored taps, every level cropped to its input size (the reference's rule for AFB2D.backward, dwt/lowlevel.py:350-365, quirk Q9)."""
+
+    @staticmethod
+    def forward(ctx, x, h0_row, h1_row, h0_col, h1_col, mode, nlev=1):
+        _check_bank_mode(mode)
+        ctx.save_for_backward(h0_row, h1_row, h0_col, h1_col)
+        ctx.shape = tuple(x.shape[-2:])
+        ctx.mode = mode
+        ctx.nlev = nlev
+        return _wpt_analysis(x, (h0_row, h1_row, h0_col, h1_col), mode, nlev)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = _wpt_synthesis(dy, ctx.saved_tensors, ctx.mode, out_hw=ctx.shape, nlev=ctx.nlev)
+        return dx, None, None, None, None, None, None
+
+
+class SFBWPT2D(Function):
+    """One or two levels of 2-D packet synthesis.  ``SFBWPT2D.apply(y (N,C,4**nlev,H',W'), g0_row, g1_row, g0_col, g1_col, mode_int,
+    out_hw, nlev) -> x``, out_hw = (H, W) to crop to or None.  Backward = the packet analysis with the stored synthesis taps of dy
+    at the size it has (the reference's SFB2D.backward, dwt/lowlevel.py:683-694)."""
+
+    @staticmethod
+    def forward(ctx, y, g0_row, g1_row, g0_col, g1_col, mode, out_hw, nlev=1):
+        _check_bank_mode(mode)
+        ctx.save_for_backward(g0_row, g1_row, g0_col, g1_col)
+        ctx.mode = mode
+        ctx.nlev = nlev
+        return _wpt_synthesis(y, (g0_row, g1_row, g0_col, g1_col), mode, out_hw=out_hw, nlev=nlev)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dx):
+        dy = None
+        if ctx.needs_input_grad[0]:
+            dy = _wpt_analysis(dx, ctx.saved_tensors, ctx.mode, ctx.nlev)
+        return dy, None, None, None, None, None, None, None
+
+
+def _filts2d(filts, prep, device):
+    """(f0_col, f1_col, f0_row, f1_row) of a 2- or 4-tuple of arrays (prepared here) or prepared tensors, as afb2d / sfb2d read it."""
+    if len(filts) not in (2, 4):
+        raise ValueError("Unknown form for input filts")
+    if any(not isinstance(f, torch.Tensor) for f in filts):
+        return prep(*filts, device=device)
+    if len(filts) == 2:
+        f0, f1 = filts
+        return f0, f1, f0.transpose(2, 3), f1.transpose(2, 3)
+    return tuple(filts)
+
+
+def wpt2d_level(x, filts, mode='zero'):
+    """Function-level packet analysis of x (N, C, H, W): ``filts`` as afb2d takes them (the *col* pair filters along H).
+    Returns (N, C, 4, H', W'), band s = 2 b_W + b_H."""
+    if x.dim() != 4:
+        raise ValueError('a packet level takes (N, C, H, W) tensors, not %d-D ones' % x.dim())
+    h0_col, h1_col, h0_row, h1_row = _filts2d(filts, prep_filt_afb2d, x.device)
+    return AFBWPT2D.apply(x, h0_row, h1_row, h0_col, h1_col, mode_to_int(mode))
+
+
+def iwpt2d_level(y, filts, mode='zero', out_hw=None):
+    """Function-level packet synthesis, the inverse of wpt2d_level: y (N, C, 4, H', W') -> (N, C, H, W), the natural size of a
+    synthesis level or out_hw = (H, W) - a size whose analysis has H' x W' coefficients."""
+    g0_col, g1_col, g0_row, g1_row = _filts2d(filts, prep_filt_sfb2d, y.device)
+    m = mode_to_int(mode)
+    if out_hw is not None:
+        out_hw = (int(out_hw[0]), int(out_hw[1]))
+        Ls = (g0_col.numel(), g0_row.numel())
+        if y.dim() == 5 and tuple(ops.coeff_len(n, L, m) for n, L in zip(out_hw, Ls)) != tuple(y.shape[-2:]):
+            raise ValueError('out_hw %s has no %d x %d coefficients' % (out_hw, y.shape[-2], y.shape[-1]))
+    return SFBWPT2D.apply(y, g0_row, g1_row, g0_col, g1_col, m, out_hw)
+
+
 # ---- the 3-D DWT: the 2-D engine on the N*C*D planes, then one depth level (csrc/wl_dwt3d.h) -------------------------
 # Sub-band s = 4 b_D + 2 b_W + b_H (b = 1: highpass) of a level: s = 0 is the low-pass, band s sits at yh[:, :, s - 1].  The 2-D
 # level's (ll, lh, hl, hh) = b_D-lowpass bands 0..3, so its dense outputs are the depth kernel's four sources as they are.

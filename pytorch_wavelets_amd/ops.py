@@ -1319,6 +1319,74 @@ def dtcwt1d_inv(lo, his, ns, rules, out_len, taps, qstart, chunk=None):
 
 
 
+# ---------------------------------------------------------------------------------------------- the 2-D wavelet packet level
+WPT_FUSED = True   # two packet levels per launch where the kernels take them (periodization, sizes multiples of 4, <= 12 taps):
+#                    measured ahead of one launch per level.  False: everything level by level, for A/B measurements.
+
+
+def _wpt_taps(t, taps):
+    """The four tap vectors for a packet launch (the C entry takes ONE tap count), or None when they differ in length."""
+    L = taps[0].numel()
+    if t.numel() == 0 or any(h.numel() != L for h in taps):
+        return None
+    return [_taps(h, t) for h in taps]
+
+
+def wpt2d_afb(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, nlev=1):
+    """`nlev` (1 or 2) packet analysis levels in ONE launch (wl_wpt2d_analysis): x (N,C,H,W) -> y (N,C,4**nlev,Kh,Kw) dense, band
+    s = 2 b_W + b_H of a level (DWTForward's order), level 1 the most significant digit of the band index.  x may be any view
+    with uniformly spaced planes and unit column stride (the previous level's y as (N,4C,Kh,Kw) is one); anything else is copied.
+    None when the launcher declines (its envelope: include/wavelets_hip.h) or the tap counts differ: callers run afb2d per level."""
+    _check_tensor(x, 'x')
+    t = _wpt_taps(x, (h_w_lo, h_w_hi, h_h_lo, h_h_hi))
+    if t is None:
+        return None
+    N, C, H, W = x.shape
+    L = t[0].numel()
+    x, x_ps, x_rs = _planes(x)
+    key = ('wpt_afb', x.device, x.dtype, N * C, H, W, x_ps, x_rs, L, mode, nlev)
+    if key in _FUSED_DECLINED:
+        return None
+    Kh, Kw = H, W
+    for _ in range(nlev):
+        Kh, Kw = coeff_len(Kh, L, mode), coeff_len(Kw, L, mode)
+    y = torch.empty((N, C, 4 ** nlev, Kh, Kw), dtype=x.dtype, device=x.device)
+    if _declined(key, 'wl_wpt2d_analysis', x, x.data_ptr(), x_ps, x_rs, y.data_ptr(), _DTYPES[x.dtype], N * C, H, W, nlev,
+                 t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), L, mode, _stream(x)):
+        return None
+    return y
+
+
+def wpt2d_sfb(y, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, out_hw=None, nlev=1):
+    """`nlev` (1 or 2) packet synthesis levels in ONE launch (wl_wpt2d_synthesis): y (N,C,4**nlev,Kh,Kw) -> x (N,C,OH,OW), the
+    natural size of the synthesis or the crop out_hw = (OH, OW).  y is read dense (a view is copied once).  None when the launcher
+    declines or the tap counts differ: callers run sfb2d per level."""
+    _check_tensor(y, 'y')
+    N, C, B, Kh, Kw = y.shape
+    if B != 4 ** nlev:
+        raise ValueError('wpt2d_sfb: %d bands are not the 4**%d of %d level(s)' % (B, nlev, nlev))
+    t = _wpt_taps(y, (g_w_lo, g_w_hi, g_h_lo, g_h_hi))
+    if t is None:
+        return None
+    L = t[0].numel()
+    OH, OW = Kh, Kw
+    for _ in range(nlev):
+        OH, OW = synth_len(OH, L, mode), synth_len(OW, L, mode)
+    if out_hw is not None:
+        OH, OW = min(OH, out_hw[0]), min(OW, out_hw[1])
+    if OH < 1 or OW < 1:
+        return None
+    key = ('wpt_sfb', y.device, y.dtype, N * C, Kh, Kw, OH, OW, L, mode, nlev)
+    if key in _FUSED_DECLINED:
+        return None
+    y = y.contiguous()
+    x = torch.empty((N, C, OH, OW), dtype=y.dtype, device=y.device)
+    if _declined(key, 'wl_wpt2d_synthesis', y, y.data_ptr(), x.data_ptr(), _DTYPES[y.dtype], N * C, Kh, Kw, OH, OW, nlev,
+                 t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), L, mode, _stream(y)):
+        return None
+    return x
+
+
 # ---------------------------------------------------------------------------------------------- DTCWT
 def dtcwt_fwd1(x, h0, h1, mode, skip_hps=False):
     """Level-1 forward: x (N,C,H,W) -> ll (N,C,He,We), highs (N,C,6,He/2,We/2,2) or None."""
