@@ -25,7 +25,10 @@
 //   synthesis:  y[p] = sum_{t<LT, t = m mod 2} g0[t] lo[(m-t)/2] + g1[t] hi[(m-t)/2],   m = p + LT - 2, samples outside [0,K) zero
 //               periodization: m = p + LT/2 - 1 and the coefficient index wraps modulo K - the reference's fold of the wrapped
 //               tail (wl_filt1d.h) whenever that tail is no longer than the signal (2K >= LT - 2; the launcher declines the rest)
-// The sum of an output runs over the taps in the same order whatever chunk it falls into: a result does not depend on the cut.
+// The sum of an output runs over the taps in the same order whatever chunk it falls into, every term an explicit fused
+// multiply-add: a result does not depend on the cut.  (With `a += h * v` the compiler is free to contract a term or not, and it
+// chose differently in different phases of the unrolled ring - packed multiplies and separate adds in some, fused multiply-adds
+// in others -, so an output's last bit depended on the phase, that is on the chunk, it fell into: DESIGN.md 4.25.)
 #pragma once
 #include "wl_common.h"
 
@@ -128,8 +131,8 @@ struct WlAfbDepth {
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) {
                     const float v = (float)win[(2 * PHASE + j) % R].e[e];
-                    alo[e] += h0[j] * v;
-                    ahi[e] += h1[j] * v;
+                    alo[e] = __builtin_fmaf(h0[j], v, alo[e]);
+                    ahi[e] = __builtin_fmaf(h1[j], v, ahi[e]);
                 }
             }
             V ylo, yhi;
@@ -215,10 +218,10 @@ struct WlSfbDepth {
                 for (int e = 0; e < VEC; ++e) {
                     const float vl = (float)wl[(PHASE + HT - 1 - u) % R].e[e];
                     const float vh = (float)wh[(PHASE + HT - 1 - u) % R].e[e];
-                    ae[e] += g0[2 * u] * vl;
-                    ae[e] += g1[2 * u] * vh;
-                    ao[e] += g0[2 * u + 1] * vl;
-                    ao[e] += g1[2 * u + 1] * vh;
+                    ae[e] = __builtin_fmaf(g0[2 * u], vl, ae[e]);
+                    ae[e] = __builtin_fmaf(g1[2 * u], vh, ae[e]);
+                    ao[e] = __builtin_fmaf(g0[2 * u + 1], vl, ao[e]);
+                    ao[e] = __builtin_fmaf(g1[2 * u + 1], vh, ao[e]);
                 }
             }
             const int p0 = 2 * (q_first + sq) - shift;     // output index of full[2q]

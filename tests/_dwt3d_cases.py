@@ -289,6 +289,58 @@ def check_vec_bodies(dev, dtype=F32):
     assert na == 'WlAfbDepth<%s, 4, 1>' % T, na
 
 
+# ---- 4a: every compiled instantiation ------------------------------------------------------------------------------------
+GRID_WAVES = tuple('db%d' % i for i in range(1, 11))        # L = 2, 4, .., 20: one case of the dispatchers' switch each
+GRID_DTYPES = (F32, F16, BF16)
+
+
+def ntaps(wave):
+    return len(taps(wave)[0])
+
+
+def depth_vec(dtype, L, inner):
+    """The body width the launcher has to pick for dense, aligned (outer, n, inner) data - the rule as DESIGN.md 4.25 states it,
+    written out here and not read from a launch: 16-byte pieces (4 floats, 8 halves), 2-byte data of 14 taps and more 8-byte
+    pieces (4 halves), and the scalar body where the inner size is no multiple of the piece."""
+    if dtype == F32:
+        vec = 4
+    else:
+        vec = 8 if L < 14 else 4
+    return vec if inner % vec == 0 else 1
+
+
+def check_depth_instantiation(dev, wave, dtype, inners=(64, 68, 5)):
+    """WlAfbDepth<T, L, VEC> / WlSfbDepth<T, L, VEC> of one tap count and element type in every body it is compiled for: n = 2L + 3
+    (odd, and long enough for periodization) on inner sizes 64 (the vector body), 68 (a multiple of 4, not of 8: 2-byte data under
+    14 taps falls to the scalar body, from 14 taps on it stays on VEC = 4) and 5 (the scalar body); every mode; three chunks
+    (two seams) against the oracle and bit for bit against one chunk.  The kernel names are built from (T, L, VEC)."""
+    L = ntaps(wave)
+    n = 2 * L + 3
+    for inner in inners:
+        vec = depth_vec(dtype, L, inner)
+        want = ('WlAfbDepth<%s, %d, %d>' % (TNAME[dtype], L, vec), 'WlSfbDepth<%s, %d, %d>' % (TNAME[dtype], L, vec))
+        for mode in MODES:
+            base, na, ns = depth_pair(dev, (2, n, inner), wave, mode, 1, dtype)
+            assert (na, ns) == want, (inner, mode, na, ns, want)
+            outs, na, ns = depth_pair(dev, (2, n, inner), wave, mode, 3, dtype)
+            assert (na, ns) == want, (inner, mode, na, ns, want)
+            for a, b in zip(outs, base):
+                assert torch.equal(a, b), 'chunks=3 differs from chunks=1 (%s %s %s inner=%d)' % (wave, dtype, mode, inner)
+
+
+def check_module_instantiation(dev, wave, dtype):
+    """One level of DWT3DForward / DWT3DInverse on the 2-byte depth kernels of this tap count: (1, 2, 2L + 3, 9, 16), symmetric."""
+    L = ntaps(wave)
+    shape = (1, 2, 2 * L + 3, 9, 16)
+    _, _, _, ks = check_forward(dev, shape, wave, 1, 'symmetric', dtype)
+    assert ks[-1].startswith('WlAfbDepth<%s, %d,' % (TNAME[dtype], L)) and depth(ks) == ['WlAfbDepth'], ks
+    c0 = pw.launch_count()
+    check_inverse(dev, shape, wave, 'symmetric', J=1, dtype=dtype)
+    ks = names(pw.kernels_since(c0))
+    # (check_inverse runs a forward for the shapes first: the last depth launch is the inverse's)
+    assert [k for k in ks if 'Depth' in k][-1].startswith('WlSfbDepth<%s, %d,' % (TNAME[dtype], L)), ks
+
+
 # ---- 5: inverse ----------------------------------------------------------------------------------------------------------
 def check_inverse(dev, shape, wave, mode, J=2, drop=None, dtype=F32):
     """DWT3DInverse of random coefficients shaped like a forward's (odd sizes: the low-pass of a level is one sample longer

@@ -270,15 +270,16 @@ def check_two_level_sequence(dev, shape=(1, 2, 72, 200), J=3):
         close(a, npy(b), F32, 'two levels per launch against level by level')
 
 
-def check_two_level_low_precision(dev, dtype, shape=(2, 3, 20, 28)):
+def check_two_level_low_precision(dev, dtype, shape=(2, 3, 20, 28), wave='db2'):
+    L = ntaps(wave)
     with fused(True):
-        x, y, ks = check_forward(dev, shape, 'db2', 2, 'periodization', dtype)
-        assert ks == ['WlWptAfb<%s, 4, 2>' % TNAME[dtype]], ks
-        _, ifm = modules(dev, 'db2', 2, 'periodization', dtype)
+        x, y, ks = check_forward(dev, shape, wave, 2, 'periodization', dtype)
+        assert ks == ['WlWptAfb<%s, %d, 2>' % (TNAME[dtype], L)], ks
+        _, ifm = modules(dev, wave, 2, 'periodization', dtype)
         c0 = pw.launch_count()
         rec = ifm(y, size=shape[2:])
-        assert names(pw.kernels_since(c0)) == ['WlWptSfb<%s, 4, 2>' % TNAME[dtype]]
-        close(rec, inv_ref(npy(y), taps('db2', syn=True, f32=True), 'periodization', level_sizes(shape[2:], 2, 4, 'periodization')),
+        assert names(pw.kernels_since(c0)) == ['WlWptSfb<%s, %d, 2>' % (TNAME[dtype], L)]
+        close(rec, inv_ref(npy(y), taps(wave, syn=True, f32=True), 'periodization', level_sizes(shape[2:], 2, L, 'periodization')),
               dtype, 'two-level inverse')
 
 
@@ -390,12 +391,12 @@ def check_low_precision(dev, dtype, mode, shape=(2, 3, 20, 28), wave='db2', J=2)
 
 def _check_low_precision(dev, dtype, mode, shape, wave, J):
     x, y, ks = check_forward(dev, shape, wave, J, mode, dtype)
-    assert ks == ['WlWptAfb<%s, 4, 1>' % TNAME[dtype]] * J, ks
+    assert ks == ['WlWptAfb<%s, %d, 1>' % (TNAME[dtype], ntaps(wave))] * J, ks
     xfm, ifm = modules(dev, wave, J, mode, dtype)
     sizes = level_sizes(shape[2:], J, ntaps(wave), mode)
     c0 = pw.launch_count()
     rec = ifm(y, size=shape[2:])
-    assert names(pw.kernels_since(c0)) == ['WlWptSfb<%s, 4, 1>' % TNAME[dtype]] * J
+    assert names(pw.kernels_since(c0)) == ['WlWptSfb<%s, %d, 1>' % (TNAME[dtype], ntaps(wave))] * J
     assert rec.dtype == dtype
     close(rec, inv_ref(npy(y), taps(wave, syn=True, f32=True), mode, sizes), dtype, 'inverse %s' % mode)
     xg = x.clone().requires_grad_(True)
@@ -404,6 +405,72 @@ def _check_low_precision(dev, dtype, mode, shape, wave, J):
     dx, = torch.autograd.grad(out, xg, cot)
     assert dx.dtype == dtype
     close(dx, fwd_grad_ref(npy(cot), sizes, taps(wave, f32=True), mode), dtype, 'dx %s' % mode)
+
+
+# ---- 7a: every compiled instantiation ------------------------------------------------------------------------------------------
+GRID_WAVES = tuple('db%d' % i for i in range(1, 11))        # L = 2, 4, .., 20: one case of the dispatchers' switch each
+GRID_WAVES2 = GRID_WAVES[:6]                                # the two-level kernels stop at 12 taps
+GRID_DTYPES = (F32, F16, BF16)
+
+
+def last_grid():
+    """Workgroups of the engine's last launch."""
+    return int(ops._backend().wl_last_grid())
+
+
+def check_wide_instantiation(dev, wave, dtype, shape=(1, 2, 37, 61)):
+    """WlWptAfb<T, L, 1> / WlWptSfb<T, L, 1> of one tap count and element type on a plane with partial last tiles in both axes
+    (level 1: one plane per workgroup, the wide walk), J = 2, a mirror mode and the wrap mode; float32 also the gradients.  The
+    kernel names are built from (T, L)."""
+    L = ntaps(wave)
+    A, Sy = ('WlWpt%s<%s, %d, 1>' % (k, TNAME[dtype], L) for k in ('Afb', 'Sfb'))
+    with fused(False):
+        for mode in ('symmetric', 'periodization'):
+            _, _, ks = check_forward(dev, shape, wave, 2, mode, dtype)
+            assert ks == [A] * 2, (mode, ks)
+            c0 = pw.launch_count()
+            check_inverse(dev, shape, wave, mode, J=2, dtype=dtype)
+            assert names(pw.kernels_since(c0)) == [Sy] * 2, (mode, pw.kernels_since(c0))
+            if dtype == F32:
+                check_gradients(dev, shape, wave, mode, J=2)
+
+
+def check_plane_run_instantiation(dev, wave, dtype, shape):
+    """The same instantiations on a run of 8 x 8 planes, several planes per workgroup (the plane-run walk): one level, 'zero' and
+    'symmetric' for every tap count, 'periodization' where the launchers take an 8 x 8 plane - the analysis up to 9 taps
+    (8 >= L - 1), the synthesis of the 4 x 4 bands up to 10 (2 * 4 >= L - 2) - and their decline asserted where they do not.  A
+    launch of fewer workgroups than planes (times tiles: one here) proves that planes shared a workgroup."""
+    L = ntaps(wave)
+    A, Sy = ('WlWpt%s<%s, %d, 1>' % (k, TNAME[dtype], L) for k in ('Afb', 'Sfb'))
+    assert tuple(shape[2:]) == (8, 8)
+    planes = shape[0] * shape[1]
+    with fused(False):
+        for mode in ('zero', 'symmetric', 'periodization'):
+            m = dwl.mode_to_int(mode)
+            if mode != 'periodization' or 8 >= L - 1:
+                _, _, ks = check_forward(dev, shape, wave, 1, mode, dtype)
+                assert ks == [A] and last_grid() < planes, (mode, ks, last_grid(), planes)
+            else:
+                h = [torch.tensor(np.ascontiguousarray(v), dtype=F32, device=dev) for v in taps(wave, f32=True)]
+                assert ops.wpt2d_afb(rand(shape, dtype, dev, 1), h[0], h[1], h[0], h[1], m) is None
+            if mode != 'periodization' or 8 >= L - 2:
+                c0 = pw.launch_count()
+                check_inverse(dev, shape, wave, mode, J=1, dtype=dtype)
+                assert names(pw.kernels_since(c0)) == [Sy] and last_grid() < planes, (mode, pw.kernels_since(c0), last_grid(), planes)
+            else:
+                g = [torch.tensor(np.ascontiguousarray(v), dtype=F32, device=dev) for v in taps(wave, syn=True, f32=True)]
+                assert ops.wpt2d_sfb(rand(tuple(shape[:2]) + (4, 4, 4), dtype, dev, 1), g[0], g[1], g[0], g[1], m) is None
+
+
+def check_two_level_instantiation(dev, wave, dtype, shape=(2, 3, 40, 72)):
+    """WlWptAfb<T, L, 2> / WlWptSfb<T, L, 2> of one tap count (up to 12) and element type: J = 2, periodization, level-2 bands of
+    10 x 18 = 2 x 2 tiles of 8 x 16 with partial last tiles in both axes, a 32 x 64 synthesis tile that overhangs both axes;
+    H / 2 = 20 >= L - 1 up to 12 taps.  Forward and inverse against the oracle, exactly one launch each; float32 also against the
+    level-by-level route (check_wrap_shapes)."""
+    if dtype == F32:
+        check_wrap_shapes(dev, wave, shape)
+    else:
+        check_two_level_low_precision(dev, dtype, shape, wave)
 
 
 # ---- 8: views --------------------------------------------------------------------------------------------------------------

@@ -1,0 +1,43 @@
+"""-m gpu: every instantiation the dispatchers of the depth kernels (csrc/wl_dwt3d.h) and of the packet kernels
+(csrc/wl_wpt2d.h) compile, on the MI355X - tap counts 2 .. 20 (the two-level packet kernels: 2 .. 12) x float32, float16, bfloat16,
+the depth kernels also per body width - against the per-axis oracle, with the kernel names built from (T, L, VEC / NLEV)
+(tests/_dwt3d_cases.py, tests/_wpt2d_cases.py).  One pytest item per (tap count, element type); log: profiles/instantiation_grid_gpu_tests.txt."""
+import pytest
+
+import _dwt3d_cases as V
+import _wpt2d_cases as P
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+IDS = dict(ids=lambda v: v if isinstance(v, str) else str(v).replace('torch.', ''))
+
+
+@pytest.mark.parametrize('dtype', V.GRID_DTYPES, **IDS)
+@pytest.mark.parametrize('wave', V.GRID_WAVES)
+def test_depth_kernels_every_tap_count_type_and_body(wave, dtype):
+    V.check_depth_instantiation(DEV, wave, dtype)
+
+
+@pytest.mark.parametrize('dtype', V.GRID_DTYPES[1:], **IDS)
+@pytest.mark.parametrize('wave', V.GRID_WAVES)
+def test_depth_kernels_in_the_modules_float16_and_bfloat16(wave, dtype):
+    V.check_module_instantiation(DEV, wave, dtype)
+
+
+@pytest.mark.parametrize('dtype', P.GRID_DTYPES, **IDS)
+@pytest.mark.parametrize('wave', P.GRID_WAVES)
+def test_one_level_packet_kernels_wide_walk(wave, dtype):
+    P.check_wide_instantiation(DEV, wave, dtype)
+
+
+@pytest.mark.parametrize('dtype', P.GRID_DTYPES, **IDS)
+@pytest.mark.parametrize('wave', P.GRID_WAVES)
+def test_one_level_packet_kernels_plane_run_walk(wave, dtype):
+    """1024 planes of 8 x 8: several planes per workgroup on the whole chip."""
+    P.check_plane_run_instantiation(DEV, wave, dtype, (16, 64, 8, 8))
+
+
+@pytest.mark.parametrize('dtype', P.GRID_DTYPES, **IDS)
+@pytest.mark.parametrize('wave', P.GRID_WAVES2)
+def test_two_level_packet_kernels(wave, dtype):
+    P.check_two_level_instantiation(DEV, wave, dtype)

@@ -3,8 +3,12 @@ every schedule it can take (tests/emu/wl_backend_emu.h, emu_backend.schedule): t
 forward, backward, shuffled by waves, and LDS-DMA copies landing at the latest legal moment (late) or the earliest (eager).
 A race between waves then shows as a difference: every case must give BITWISE the same results under every schedule (no
 kernel here reduces with atomics) and pass the oracle checks of its shared helper.  Each case asserts by name the kernel
-it is there for, so a later dispatch change fails it instead of leaving it vacuous."""
+it is there for, so a later dispatch change fails it instead of leaving it vacuous.  test_every_barrier_kernel_has_a_case reads
+the kernel headers and fails when a functor whose body has a barrier is named by no case."""
 import contextlib
+import glob
+import os
+import re
 
 import numpy as np
 import pytest
@@ -14,12 +18,17 @@ import emu_backend
 import pytorch_wavelets_amd as pw
 from pytorch_wavelets_amd import ops
 
+import _bf16_cases as B
+import _dtcwt1d_cases as D1
 import _dtcwt_cases as D
 import _ext_cases as E
 import _lattice_cases as LC
 import _nearsymb_cases as NB
 import _packed_cases as PK
 import _per_cases as PC
+import _swt_inv_cases as SI
+import _wpt2d_cases as WP
+from pytorch_wavelets_amd.dwt import lowlevel as dwl
 
 SCHEDULES = [('alternate', 'late', 0), ('forward', 'late', 0), ('reverse', 'late', 0), ('forward', 'eager', 0),
              ('reverse', 'eager', 0), ('shuffled', 'eager', 1), ('shuffled', 'eager', 2)]
@@ -108,6 +117,7 @@ def _t(kernel, pred=None, dtype=None, grid=None):
         if grid is not None and (g is None or not grid(g)):
             return False
         return pred is None or pred(k)
+    ok.kernel = kernel
     ok.what = kernel + (' (%s)' % pred.__name__ if pred else '') + (' ' + dtype if dtype else '') + (' (%s)' % grid.__name__ if grid else '')
     return ok
 
@@ -246,6 +256,80 @@ def _scatj2_rot(shape=(2, 1, 64, 80)):
     return ks
 
 
+def _nlev(n):
+    def pred(k):
+        return k.rstrip().endswith(', %d>' % n)
+    pred.__name__ = 'NLEV=%d' % n
+    return pred
+
+
+def _wpt(wave, mode, shape, J, two):
+    """WPT2DForward / WPT2DInverse and both backwards (each runs the other direction's kernel) against the oracle; two: two
+    levels per launch where the kernels take them."""
+    with WP.fused(two):
+        WP.check_forward('cpu', shape, wave, J, mode)
+        WP.check_inverse('cpu', shape, wave, mode, J=J)
+        WP.check_gradients('cpu', shape, wave, mode, J=J)
+
+
+def _wpt_f16():
+    with WP.fused(False):
+        WP.check_low_precision('cpu', F16, 'symmetric')
+
+
+def _dt1d(n, J, biort, qshift, chunks, shape):
+    """DTCWT1DForward, DTCWT1DInverse and dx with cotangents on every output (tests/_dtcwt1d_cases.run_both), chunk lengths
+    forced (analysis pairs, synthesis samples; 0: the engine's), against the oracle."""
+    x, yl, yh, rec, dx, cots = D1.run_both('cpu', n, J, biort, qshift, F32, chunks, shape=shape)
+    t = D1.taps(biort, qshift, f32=True)
+    rl, rh = D1.fwd_ref(D1.npy(x), J, t)
+    D1.close(yl, rl, F32, 'yl')
+    for j in range(J):
+        D1.close(yh[j], rh[j], F32, 'yh[%d]' % j)
+    D1.close(rec, D1.inv_ref(D1.npy(yl), [D1.npy(h) for h in yh], D1.taps(biort, qshift, syn=True, f32=True)), F32, 'rec')
+    D1.close(dx, D1.fwd_grad_ref(D1.npy(cots[0]), [D1.npy(c) for c in cots[1:]], n, t), F32, 'dx')
+
+
+def _swt_inverse(shape=(1, 2, 20, 24)):
+    """SWTInverse (one WlSwtInvLevel launch per level), the transposed level against the oracle's transpose, and the backward of
+    SWTForward (J = 2) - at the smallest periodic shape of tests/test_swt_inverse_emu.py."""
+    _, rec = SI.check_roundtrip('cpu', 'db2', 2, shape, torch.float64)
+    SI.check_adjoint('cpu', 'db2', 'db2', 'periodic', 1, shape, torch.float64)
+    rng = np.random.RandomState(8)
+    xfm, _ = SI.swt_modules('cpu', 'db2', 'db2', 2)
+    x = torch.tensor(rng.randn(*shape), requires_grad=True)
+    ys = xfm(x)
+    cots = [torch.tensor(rng.randn(*y.shape)) for y in ys]
+    c0 = pw.launch_count()
+    dx, = torch.autograd.grad(ys, x, cots)
+    ks = pw.kernels_since(c0)
+    assert len(ks) == 2 and all(k.startswith('WlSwtInvLevel') for k in ks), ks
+    lhs, rhs = sum(float((y.detach() * c).sum()) for y, c in zip(ys, cots)), float((x.detach() * dx).sum())
+    assert abs(lhs - rhs) <= 1e-11 * max(1.0, abs(lhs)), (lhs, rhs)                # <A x, y> = <x, A^T y>
+    _record(rec, dx)
+
+
+def _dwt_per_level(wave, mode, shape, J, generic=False):
+    """DWTForward + DWTInverse one launch per level, planes kept off the several-planes-per-workgroup kernels: the tile kernels
+    WlAfbTile / WlSfbTile, or - generic - the runtime-tap ones."""
+    import _opts
+    with B._setattrs(dwl, FUSED_LEVELS=False), B.no_small():
+        _opts.set_generic(int(generic))
+        try:
+            _dwt_fwd_inv(wave, mode, shape, J)
+        finally:
+            _opts.set_generic(0)
+
+
+def _dtcwt_generic(shape):
+    import _opts
+    _opts.set_generic(1)
+    try:
+        _dtcwt_fwd_inv(shape, 'near_sym_a', 'qshift_a', 2, stream=False)
+    finally:
+        _opts.set_generic(0)
+
+
 F32 = torch.float32
 F16 = torch.float16
 CASES = [
@@ -293,6 +377,27 @@ CASES = [
     ('dt_small', lambda: _dtcwt_fwd_inv((6, 3, 32, 32), 'near_sym_a', 'qshift_a', 1, stream=False), [_t('WlDtFwd1Small')]),
     ('rot_level1', lambda: [E.check_rot(n, 'cpu', F32, 1e-5) for n in E.ROT_CASES[:1]], [_t('WlDtFwd1Rot')]),
     ('swt', lambda: [E.check_swt(n, 'cpu', F32, 1e-5) for n in E.SWT_CASES[:1]], [_t('WlSwtLevel')]),
+    ('swt_inverse', _swt_inverse, [_t('WlSwtInvLevel')]),
+    # ---- WlWptAfb / WlWptSfb: two levels per launch (five barrier phases, the staging words reused for the level-2 rows; 12 taps:
+    # the largest aliased region), one level per launch on the wide walk and on the plane-run walk (8 planes on 2 workgroups)
+    ('wpt_two_level_db4', lambda: _wpt('db4', 'periodization', (1, 2, 40, 72), 2, True), [_t('WlWptAfb', _nlev(2)), _t('WlWptSfb', _nlev(2))]),
+    ('wpt_two_level_db6', lambda: _wpt('db6', 'periodization', (1, 2, 40, 72), 2, True), [_t('WlWptAfb', _nlev(2)), _t('WlWptSfb', _nlev(2))]),
+    ('wpt_wide', lambda: _wpt('db4', 'symmetric', (1, 2, 37, 61), 2, False), [_t('WlWptAfb', _nlev(1)), _t('WlWptSfb', _nlev(1))]),
+    ('wpt_plane_run', lambda: _wpt('db2', 'symmetric', (2, 4, 8, 8), 1, False),
+     [_t('WlWptAfb', _nlev(1), grid=_below(8)), _t('WlWptSfb', _nlev(1), grid=_below(8))]),
+    ('wpt_f16', _wpt_f16, [_t('WlWptAfb', _nlev(1), dtype='_Float16'), _t('WlWptSfb', _nlev(1), dtype='_Float16')]),
+    # ---- WlDt1dFwd / WlDt1dInv: a geometry block written by lane 0, up to four level buffers, `put` into up to three cells
+    ('dt1d_chunks_J3', lambda: _dt1d(301, 3, 'near_sym_a', 'qshift_a', (5, 44), (2, 1, 301)), [_with('WlDt1dFwd', 1, '10'), _with('WlDt1dInv', 1, '10')]),
+    ('dt1d_J4_q14', lambda: _dt1d(301, 4, 'near_sym_b', 'qshift_b', (5, 44), (2, 1, 301)), [_with('WlDt1dFwd', 1, '14'), _with('WlDt1dInv', 1, '14')]),
+    ('dt1d_two_groups_J6', lambda: _dt1d(512, 6, 'near_sym_a', 'qshift_a', (0, 0), (1, 2, 512)), [_t('WlDt1dFwd'), _t('WlDt1dInv')]),
+    ('dt1d_none_high', lambda: D1.check_none_highs('cpu', 1), [_t('WlDt1dFwd'), _t('WlDt1dInv')]),
+    # ---- the per-level kernels: the tile kernels and the runtime-tap (generic) ones, on the smallest planes that reach them
+    ('dwt_tile', lambda: _dwt_per_level('db4', 'symmetric', (1, 2, 20, 36), 2), [_t('WlAfbTile'), _t('WlSfbTile')]),
+    ('dwt_generic', lambda: _dwt_per_level('db3', 'reflect', (1, 2, 20, 36), 2, generic=True), [_t('WlAfb2dTile'), _t('WlSfb2dTile')]),
+    ('dt_tile', lambda: _dtcwt_fwd_inv((1, 2, 40, 56), 'near_sym_a', 'qshift_a', 2, stream=False),
+     [_t('WlDtFwd1Tile'), _t('WlDtFwd2Tile'), _t('WlDtInv1Tile'), _t('WlDtInv2Tile')]),
+    ('dt_generic', lambda: _dtcwt_generic((1, 2, 24, 40)), [_t('WlDtFwd1'), _t('WlDtFwd2'), _t('WlDtInv1'), _t('WlDtInv2')]),
+    ('dt_level1_strip', lambda: _dtcwt_fwd_inv((1, 2, 24, 256), 'near_sym_a', 'qshift_a', 1), [_t('WlDtFwd1Strip'), _t('WlDtInv1Strip')]),
 ]
 
 
@@ -331,3 +436,43 @@ def test_ring_slot_is_a_floor_mod():
     for rows in range(2, 65):
         bad = [r for r in rs if slot(r, rows) != r % rows]
         assert not bad, (rows, bad[:5], [slot(r, rows) for r in bad[:5]])
+
+
+# Barrier functors that need no case here, each with the reason.
+EXEMPT = {}
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'pytorch_wavelets_amd', 'csrc')
+
+
+def barrier_functors(csrc=CSRC):
+    """Every kernel functor of the engine whose body has a barrier - a plain text scan of the kernel sources.  A file is cut into
+    regions at every `struct Wl...` and every `wl_..._body(` function defined at the start of a line; a body function whose region
+    calls ctx.sync() is a barrier body; a struct is a barrier functor when its region calls ctx.sync() or a barrier body - the
+    WL_FUNCTOR(name, args, body) lines of wl_api.inc included.  -> {functor: file}"""
+    head = re.compile(r'^(?:struct (Wl\w+)[^;\n]*$|(?:WL_DEV|WL_HD|static|inline)[^;\n]*?\b(wl_\w+_body)\()', re.M)
+    regions = []
+    for path in sorted(glob.glob(os.path.join(csrc, '*.h')) + glob.glob(os.path.join(csrc, '*.inc'))):
+        text = open(path).read()
+        marks = list(head.finditer(text))
+        for m, nxt in zip(marks, marks[1:] + [None]):
+            regions.append((m.group(1), m.group(2), text[m.end():nxt.start() if nxt else len(text)], os.path.basename(path)))
+        for m in re.finditer(r'^WL_FUNCTOR\((Wl\w+), \w+, (wl_\w+)\)', text, re.M):
+            regions.append((m.group(1), None, m.group(2) + '(', os.path.basename(path)))
+    bodies = set(fn for _, fn, body, _ in regions if fn and 'ctx.sync()' in body)
+    return dict((st, f) for st, _, body, f in regions
+                if st and not st.endswith('Args') and ('ctx.sync()' in body or any(b + '<' in body or b + '(' in body for b in bodies)))
+
+
+def test_every_barrier_kernel_has_a_case():
+    """The next kernel with a barrier cannot slip past this suite: every functor of csrc/ whose body calls ctx.sync() is named
+    by the wanted-kernel list of some case above, or stands in EXEMPT with a reason."""
+    found = barrier_functors()
+    # the scan itself: one known functor per way a barrier reaches a functor (its own body, a specialisation, a body function
+    # behind a plain struct, one behind WL_FUNCTOR), and nothing that is no kernel
+    for name in ('WlAfbRows', 'WlWptAfb', 'WlWptSfb', 'WlDt1dFwd', 'WlDt1dInv', 'WlSwtInvLevel', 'WlAfb2dTile', 'WlDtInv2', 'WlDtFwd1Tile'):
+        assert name in found, (name, sorted(found))
+    assert len(found) >= 33 and not any(n in found for n in ('WlAfbDepth', 'WlSfbDepth', 'WlCorr1d', 'WlCtx')), sorted(found)
+    named = set(w.kernel for _, _, want in CASES for w in want)
+    missing = sorted(k for k in found if k not in named and k not in EXEMPT)
+    assert not missing, 'barrier kernels without a schedule case: %s' % ', '.join('%s (%s)' % (k, found[k]) for k in missing)
+    stale = sorted(k for k in EXEMPT if k not in found or k in named)
+    assert not stale, ('exempt, but covered or gone', stale)
