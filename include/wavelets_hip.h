@@ -50,7 +50,8 @@ extern "C" {
  *   220 (this header): dtype WL_BF16 (bfloat16 data, float taps) everywhere WL_F16 is accepted; no argument list changes.
  *          Later under 220, new names only: wl_dwt3d_depth_analysis / wl_dwt3d_depth_synthesis (the depth axis of the 3-D DWT;
  *          a caller that needs them looks the symbols up); wl_dtcwt1d_analysis / wl_dtcwt1d_synthesis (the 1-D DTCWT) and
- *          wl_wpt2d_analysis / wl_wpt2d_synthesis (the 2-D wavelet packet level) likewise. */
+ *          wl_wpt2d_analysis / wl_wpt2d_synthesis (the 2-D wavelet packet level) likewise; wl_swt1d_analysis / wl_swt1d_adjoint
+ *          (the 1-D stationary transform) likewise. */
 int wl_version(void);
 const char* wl_backend(void);
 
@@ -372,6 +373,24 @@ int wl_dtcwt1d_analysis(const void* x, void* const* his, void* const* los, int d
 int wl_dtcwt1d_synthesis(const void* lo, int n_lo, const void* const* his, const int* n, const int* rule, void* y, int out_len,
                          int dtype, int64_t rows, int J, int qstart, const void* g0o, const void* g1o, int L0, int L1,
                          const void* g0a, const void* g0b, const void* g1a, const void* g1b, int M, int chunk, void* stream);
+
+/* The 1-D stationary (undecimated) wavelet transform along the last axis, periodic, J (1..3) levels in ONE launch on wave tiles
+ * (csrc/wl_swt1d.h: a wave holds 1024 consecutive positions of a row in registers and fetches its neighbours' with wave shuffles;
+ * no LDS, no barrier).  Level j has dilation 2^(j-1); the taps are the stored (reversed) float taps of wl_corr1d.
+ *   wl_swt1d_analysis: x (rows,N) -> lo (rows,N), the level-J lowpass, and his[j] (rows,N), j = 0..J-1 finest first (NULL = not
+ *     stored); per level lo_j[p], hi_j[p] = scale * sum_t h0[t], h1[t] * lo_{j-1}[(p - (L/2 - 1) d + d t) mod N].  Replaces J
+ *     chained wl_corr1d calls with tap_step = d (afb1d_atrous level by level: every intermediate lowpass through memory twice).
+ *   wl_swt1d_adjoint: lo (rows,N) and his[j] (rows,N) or NULL = zeros -> y (rows,N), coarsest level first
+ *     lo_{j-1}[m] = scale * sum_t (g0[t] lo_j[(m + (L/2 - 1) d - d t) mod N] + g1[t] hi_j[..]).  Replaces J chained wl_corr1d_adj
+ *     calls: the backward of the analysis (its taps, scale 1) and the inverse transform (synthesis taps, scale 1/2).
+ * ext: the extension code of wl_corr1d; origin: the first tile starts that many positions further left (0; tests move the tile
+ * seams with it, the results do not change by a bit), 0 <= origin < 1024 - (L - 1)(2^J - 1).
+ * float32 / float16 / bfloat16, even L <= 20.  WL_ERR_UNSUPPORTED for float64, odd L, L > 20, J > 3, an extension other than
+ * periodic (3) and rows of 2^30 samples and more: callers then go level by level. */
+int wl_swt1d_analysis(const void* x, void* lo, void* const* his, int dtype, int64_t rows, int N, int J, const void* h0,
+                      const void* h1, int L, int ext, double scale, int origin, void* stream);
+int wl_swt1d_adjoint(const void* lo, const void* const* his, void* y, int dtype, int64_t rows, int N, int J, const void* g0,
+                     const void* g1, int L, int ext, double scale, int origin, void* stream);
 
 /* ---- single-axis building blocks -------------------------------------------------------------------------------
  * One strided / dilated correlation with boundary extension along the middle axis of a dense (outer, n, inner) tensor:

@@ -55,7 +55,9 @@ PROTOTYPES = {
     'wl_dwt3d_depth_synthesis': (I, [PP, PL, PL, PP, PL, PL, PP, PL, PL, I, I, L, I, L, I, P, I, P, I, I, I, P]),
     'wl_dtcwt1d_analysis': (I, [P, PP, PP, I, L, I, I, I, C.POINTER(I), P, P, I, I, P, P, P, P, I, I, P]),
     'wl_dtcwt1d_synthesis': (I, [P, I, PP, C.POINTER(I), C.POINTER(I), P, I, I, L, I, I, P, P, I, I, P, P, P, P, I, I, P]),
-    'wl_wpt2d_analysis': (I, [P, L, I, P, I, L, I, I, I, P, P, P, P, I, I, P]),
+    'wl_swt1d_analysis': (I, [P, P, PP, I, L, I, I, P, P, I, I, C.c_double, I, P]),
+    'wl_swt1d_adjoint': (I, [P, PP, P, I, L, I, I, P, P, I, I, C.c_double, I, P]),
+    'wl_wpt2d_analysis':(I, [P, L, I, P, I, L, I, I, I, P, P, P, P, I, I, P]),
     'wl_wpt2d_synthesis': (I, [P, P, I, L, I, I, I, I, I, P, P, P, P, I, I, P]),
     'wl_scat_bwd_level1': (I, [P, P, P, P, I, L, I, I, I, P, I, P, I, I, I, P]),
 }

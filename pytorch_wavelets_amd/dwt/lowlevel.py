@@ -662,6 +662,135 @@ def sfb1d_atrous(lo, hi, g0, g1, mode='periodic', dim=-1, dilation=1):
     return SFB1DAtrous.apply(lo, hi, t0, t1, dim % lo.dim(), dilation)
 
 
+# ---- the 1-D stationary transform along the last axis ----------------------------------------------------------------------------
+# Level j = afb1d_atrous with dilation 2**(j-1) on the previous lowpass.  Periodic, even L <= 20, not float64: the first (up to)
+# three levels are ONE launch of the wave-tile kernels (csrc/wl_swt1d.h: x read once, the intermediate lowpasses stay fp32 in
+# registers); deeper levels and everything else go level by level on corr1d / corr1d_adj, with the same answer.
+def _swt1d_fused_levels(t, L, ext, J):
+    if not ops.SWT1D_FUSED or ext != ops.EXT_PERIODIC or t.dtype == torch.float64 or L % 2 or L > 20:
+        return 0
+    return min(J, ops.SWT1D_MAXJ)
+
+
+def _swt1d_analysis(x, h0, h1, ext, J, scale=1.0):
+    """J levels of scale * the a-trous bank along the last axis, no autograd -> (lo, [hi_1 ..], [n_0 ..]): n_j = the length of
+    the input of level j + 1 (odd tap counts lose a sample per level)."""
+    L = h0.numel()
+    lo, his, ns, j = x, [], [], 0
+    nf = _swt1d_fused_levels(x, L, ext, J)
+    if nf:
+        res = ops.swt1d_fwd(x, h0, h1, nf, scale=scale)
+        if res is not None:
+            lo, his = res[0], list(res[1])
+            ns, j = [x.shape[-1]] * nf, nf
+    while j < J:
+        n = lo.shape[-1]
+        K, start = _atrous_geom(n, L, 2 ** j)
+        if K < 1:
+            raise ValueError("level {} of the stationary transform is left without samples".format(j + 1))
+        lo, hi = ops.corr1d(lo, -1, h0, h1, K, start, 1, 2 ** j, ext)
+        if scale != 1.0:
+            lo.mul_(scale), hi.mul_(scale)
+        his.append(hi)
+        ns.append(n)
+        j += 1
+    return lo, his, ns
+
+
+def _swt1d_adjoint(lo, his, g0, g1, ext, ns, scale=1.0):
+    """The transpose of _swt1d_analysis times scale per level: his finest first, None = zeros; ns[j] = the length of the output
+    of level j + 1's transpose."""
+    J, L = len(his), g0.numel()
+    nf = _swt1d_fused_levels(lo, L, ext, J)
+    j = J
+    while j > 0:
+        if j == nf:
+            y = ops.swt1d_adj(lo, his[:nf], g0, g1, scale)
+            if y is not None:
+                return y
+        hi = his[j - 1]
+        start = _atrous_geom(ns[j - 1], L, 2 ** (j - 1))[1]
+        lo = ops.corr1d_adj(lo, hi, -1, g0, None if hi is None else g1, ns[j - 1], start, 2 ** (j - 1), ext, scale)
+        j -= 1
+    return lo
+
+
+class SWT1DMulti(Function):
+    """``SWT1DMulti.apply(x, h0, h1, ext, J) -> (lo, hi_1 .. hi_J)``: all levels of the 1-D stationary analysis as ONE autograd
+    node.  Backward = the transposed cascade with the same taps."""
+
+    @staticmethod
+    def forward(ctx, x, h0, h1, ext, J):
+        ctx.save_for_backward(h0, h1)
+        lo, his, ns = _swt1d_analysis(x, h0, h1, ext, J)
+        ctx.geom = (ext, ns)
+        return (lo,) + tuple(his)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dlo, *dhis):
+        dx = None
+        if ctx.needs_input_grad[0]:
+            h0, h1 = ctx.saved_tensors
+            ext, ns = ctx.geom
+            dx = _swt1d_adjoint(dlo, list(dhis), h0, h1, ext, ns)
+        return dx, None, None, None, None
+
+
+class ISWT1DMulti(Function):
+    """``ISWT1DMulti.apply(lo, g0, g1, *his) -> x``: all levels of the inverse 1-D stationary transform, coarsest first
+    lo_{j-1} = 1/2 (A_0(g)^T lo_j + A_1(g)^T hi_j), as ONE autograd node; his finest first, None = zeros.  Backward = 1/2 per
+    level of the analysis cascade with the synthesis taps."""
+
+    @staticmethod
+    def forward(ctx, lo, g0, g1, *his):
+        ctx.save_for_backward(g0, g1)
+        ctx.present = [h is not None for h in his]
+        n = lo.shape[-1]
+        return _swt1d_adjoint(lo, list(his), g0, g1, ops.EXT_PERIODIC, [n] * len(his), 0.5)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dx):
+        g0, g1 = ctx.saved_tensors
+        dlo, dhis, _ = _swt1d_analysis(dx, g0, g1, ops.EXT_PERIODIC, len(ctx.present), 0.5)
+        # (level j's bands carry the factors of the levels above it as well: they were applied on the way down)
+        return (dlo, None, None) + tuple(d if p else None for d, p in zip(dhis, ctx.present))
+
+
+def _check_swt1d_input(t, name):
+    if t.dim() != 3:
+        raise ValueError("{} must be (N, C, L), not {}".format(name, tuple(t.shape)))
+
+
+def swt1d(x, h0, h1, mode='periodic', J=1):
+    """J levels of the 1-D stationary (undecimated) transform of x (N, C, L) along L: (yl, [yh_1 .. yh_J]) finest first, every
+    tensor (N, C, L).  Level j is afb1d_atrous with dilation 2**(j-1) on the previous lowpass (stored taps, the six pad modes of
+    afb1d_atrous; any other mode raises its ValueError).  Differentiable in x."""
+    if mode not in _ATROUS_EXT:
+        raise ValueError("Unkown pad type: {}".format(mode))
+    _check_swt1d_input(x, 'x')
+    if J < 1:
+        return x, []
+    outs = SWT1DMulti.apply(x, _as_taps(h0, x), _as_taps(h1, x), _ATROUS_EXT[mode], J)
+    return outs[0], list(outs[1:])
+
+
+def iswt1d(yl, yh, g0, g1, mode='periodic'):
+    """The inverse of swt1d: yl (N, C, L) and yh = [finest .. coarsest] (None = zeros) -> x (N, C, L), per level, coarsest first,
+    lo_{j-1} = 1/2 (A_0(g)^T lo_j + A_1(g)^T hi_j) - the 1-D case of sfb1d_atrous.  'periodic' and even tap counts only."""
+    t0, t1 = _as_syn_taps(g0, yl), _as_syn_taps(g1, yl)
+    _check_atrous_inverse(mode, t0, t1)
+    _check_swt1d_input(yl, 'yl')
+    yh = list(yh)
+    for h in yh:
+        if h is not None and h.shape != yl.shape:
+            raise ValueError("yl is {} and a level of yh is {}".format(tuple(yl.shape), tuple(h.shape)))
+    if not yh:
+        return yl
+    return ISWT1DMulti.apply(yl, t0, t1, *yh)
+
+
 class SWTInvMulti(Function):
     """All levels of the inverse stationary transform as ONE autograd node: ``SWTInvMulti.apply(g0_row, g1_row, g0_col, g1_col,
     dilation, *coeffs) -> x`` with coeffs[j] (N,4C,H,W), finest first, level j dilated by dilation * 2**j.  It starts from the ll

@@ -1318,6 +1318,73 @@ def dtcwt1d_inv(lo, his, ns, rules, out_len, taps, qstart, chunk=None):
     return y
 
 
+# ---------------------------------------------------------------------------------------------- the 1-D stationary transform
+SWT1D_FUSED = True   # up to three periodic levels per launch on the wave-tile kernels (csrc/wl_swt1d.h).  False: everything level
+#                      by level on corr1d / corr1d_adj, for A/B measurements and tests.
+SWT1D_TILE = 1024    # positions a wave holds: 64 lanes x WL_SWT1D_V of csrc/wl_swt1d.h
+SWT1D_MAXJ = 3       # WL_SWT1D_MAXJ
+
+
+def swt1d_core(L, J):
+    """Positions of a wave's tile that are still valid after J levels of an L-tap bank: what a tile stores, and what the tiles
+    of a row advance by (the seams of a row lie at multiples of it, minus `origin`)."""
+    return SWT1D_TILE - (L - 1) * (2 ** J - 1)
+
+
+def _swt1d_covered(t, L, L1, J):
+    return not (t.dtype == torch.float64 or t.numel() == 0 or J < 1 or J > SWT1D_MAXJ or L % 2 or L > 20 or L1 != L
+                or t.shape[-1] >= 1 << 30)
+
+
+def swt1d_fwd(x, h0, h1, nlev, origin=0, scale=1.0):
+    """`nlev` (1..3) levels of the periodic a-trous analysis along the LAST axis in ONE launch (wl_swt1d_analysis): x (..., n) ->
+    (lo, [hi_1 .. hi_nlev]) finest first, all (..., n); level j has dilation 2**(j-1) and is multiplied by `scale`.  None when
+    the launcher declines (float64, odd or long filters, more levels): callers go level by level on corr1d.  `origin` (tests)
+    moves the tile seams."""
+    _check_tensor(x, 'x')
+    L, n = h0.numel(), x.shape[-1]
+    if not _swt1d_covered(x, L, h1.numel(), nlev):
+        return None
+    x = x.contiguous()
+    rows = x.numel() // n
+    key = ('swt1d_fwd', x.device, x.dtype, rows, n, L, nlev)
+    if key in _FUSED_DECLINED:
+        return None
+    t0, t1 = _taps(h0, x), _taps(h1, x)
+    lo = torch.empty_like(x)
+    his = [torch.empty_like(x) for _ in range(nlev)]
+    if _declined(key, 'wl_swt1d_analysis', x, x.data_ptr(), lo.data_ptr(), _ptr_array(his), _DTYPES[x.dtype], rows, n, nlev,
+                 t0.data_ptr(), t1.data_ptr(), L, EXT_PERIODIC, float(scale), int(origin), _stream(x)):
+        return None
+    return lo, his
+
+
+def swt1d_adj(lo, his, g0, g1, scale, origin=0):
+    """The transpose of swt1d_fwd in ONE launch (wl_swt1d_adjoint): lo (..., n), his = [finest .. coarsest] (None = zeros) ->
+    y (..., n), per level, coarsest first, lo_{j-1} = scale * (A_0(g)^T lo_j + A_1(g)^T hi_j).  None when the launcher declines."""
+    _check_tensor(lo, 'lo')
+    J, L, n = len(his), g0.numel(), lo.shape[-1]
+    if not _swt1d_covered(lo, L, g1.numel(), J):
+        return None
+    for h in his:
+        if h is not None:
+            _check_tensor(h, 'yh')
+            _same_device(lo, h)
+            if h.dtype != lo.dtype or h.shape != lo.shape:
+                return None
+    rows = lo.numel() // n
+    key = ('swt1d_adj', lo.device, lo.dtype, rows, n, L, J)
+    if key in _FUSED_DECLINED:
+        return None
+    lo = lo.contiguous()
+    his = [None if h is None else h.contiguous() for h in his]
+    t0, t1 = _taps(g0, lo), _taps(g1, lo)
+    y = torch.empty_like(lo)
+    if _declined(key, 'wl_swt1d_adjoint', lo, lo.data_ptr(), _ptr_array(his), y.data_ptr(), _DTYPES[lo.dtype], rows, n, J,
+                 t0.data_ptr(), t1.data_ptr(), L, EXT_PERIODIC, float(scale), int(origin), _stream(lo)):
+        return None
+    return y
+
 
 # ---------------------------------------------------------------------------------------------- the 2-D wavelet packet level
 WPT_FUSED = True   # two packet levels per launch where the kernels take them (periodization, sizes multiples of 4, <= 12 taps):
