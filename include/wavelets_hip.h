@@ -51,7 +51,8 @@ extern "C" {
  *          Later under 220, new names only: wl_dwt3d_depth_analysis / wl_dwt3d_depth_synthesis (the depth axis of the 3-D DWT;
  *          a caller that needs them looks the symbols up); wl_dtcwt1d_analysis / wl_dtcwt1d_synthesis (the 1-D DTCWT) and
  *          wl_wpt2d_analysis / wl_wpt2d_synthesis (the 2-D wavelet packet level) likewise; wl_swt1d_analysis / wl_swt1d_adjoint
- *          (the 1-D stationary transform) likewise. */
+ *          (the 1-D stationary transform) likewise; wl_wpt1d_analysis / wl_wpt1d_synthesis (the 1-D wavelet packet transform)
+ *          likewise. */
 int wl_version(void);
 const char* wl_backend(void);
 
@@ -391,6 +392,29 @@ int wl_swt1d_analysis(const void* x, void* lo, void* const* his, int dtype, int6
                       const void* h1, int L, int ext, double scale, int origin, void* stream);
 int wl_swt1d_adjoint(const void* lo, const void* const* his, void* y, int dtype, int64_t rows, int N, int J, const void* g0,
                      const void* g1, int L, int ext, double scale, int origin, void* stream);
+
+/* The 1-D wavelet packet transform (the full tree: every band is split again) along the last axis, periodization, nlev (1..3)
+ * levels in ONE launch on wave tiles (csrc/wl_wpt1d.h: a wave holds 1024 consecutive positions of a row in registers and fetches
+ * its neighbours' with wave shuffles; no LDS, no barrier; the intermediate levels stay fp32 in registers).  The taps are the
+ * stored float taps of wl_corr1d / wl_synth1d; a band of even length m >= L is split as
+ *     lo[k], hi[k] = sum_t h0[t], h1[t] * in[(2k + t - (L/2 - 1)) mod m].
+ *   wl_wpt1d_analysis: x (rows,len) -> y (rows, 2^nlev, len / 2^nlev) dense, band b = sum_j s_j 2^(nlev-j), s_j = 1 the highpass
+ *     taken at level j (level 1 is the most significant bit); the next launch reads y as rows * 2^nlev rows - no copy between
+ *     launches.  x is read once and y written once whatever nlev.
+ *   wl_wpt1d_synthesis: y (rows, 2^nlev, len / 2^nlev) -> x (rows,len), the exact transpose
+ *     out[i] = sum over (k,t) with 2k + t - (L/2 - 1) = i (mod m) of g0[t] lo[k] + g1[t] hi[k]
+ *     per level: the inverse transform with the stored synthesis taps, the backward of the analysis with the analysis taps; the
+ *     inverse's backward is wl_wpt1d_analysis with the synthesis taps.
+ * mode: the filter-bank mode of wl_dwt2d_analysis (2 = periodization, the only one taken); origin: the first tile starts that
+ * many positions further left (0; tests move the tile seams with it, the results do not change by a bit), a multiple of 2^nlev
+ * below the tile's core, 1024 - 2 * roundup((L/2)(2^nlev - 1), 2^nlev).
+ * float32 / float16 / bfloat16, even L <= 20.  WL_ERR_UNSUPPORTED for float64, odd L, L > 20, nlev > 3, another mode, len no
+ * multiple of 2^nlev, a last level whose input len / 2^(nlev-1) is shorter than L (the reference's single fold is not the
+ * circular form there) and rows of 2^30 samples and more: callers then go level by level on wl_corr1d / wl_synth1d. */
+int wl_wpt1d_analysis(const void* x, void* y, int dtype, int64_t rows, int len, int nlev, const void* h0, const void* h1, int L,
+                      int mode, int origin, void* stream);
+int wl_wpt1d_synthesis(const void* y, void* x, int dtype, int64_t rows, int len, int nlev, const void* g0, const void* g1, int L,
+                       int mode, int origin, void* stream);
 
 /* ---- single-axis building blocks -------------------------------------------------------------------------------
  * One strided / dilated correlation with boundary extension along the middle axis of a dense (outer, n, inner) tensor:

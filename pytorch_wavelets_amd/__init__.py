@@ -11,6 +11,7 @@ from .dwt.transform1d import DWT1DForward, DWT1DInverse   # noqa: E402,F401
 from .dwt.swt1d import SWT1DForward, SWT1DInverse   # noqa: E402,F401
 from .dwt.transform3d import DWT3DForward, DWT3DInverse   # noqa: E402,F401
 from .dwt.packet2d import WPT2DForward, WPT2DInverse, wpt2d_freq_order   # noqa: E402,F401
+from .dwt.packet1d import WPT1DForward, WPT1DInverse, wpt1d_freq_order   # noqa: E402,F401
 from .dtcwt.transform2d import DTCWTForward, DTCWTInverse   # noqa: E402,F401
 from .dtcwt.transform1d import DTCWT1DForward, DTCWT1DInverse   # noqa: E402,F401
 from .scatternet import ScatLayer, ScatLayerj2   # noqa: E402,F401
@@ -65,9 +66,11 @@ WPT2D = WPT2DForward
 IWPT2D = WPT2DInverse
 SWT1D = SWT1DForward
 ISWT1D = SWT1DInverse
+WPT1D = WPT1DForward
+IWPT1D = WPT1DInverse
 
 __all__ = ['__version__', 'last_kernel', 'launch_count', 'kernels_since', 'DTCWTForward', 'DTCWTInverse', 'DWTForward', 'DWTInverse', 'DTCWT', 'IDTCWT',
            'DWT', 'IDWT', 'DWT2D', 'IDWT2D', 'DWT1DForward', 'DWT1DInverse', 'DWT1D', 'IDWT1D', 'ScatLayer', 'ScatLayerj2',
            'DWT3DForward', 'DWT3DInverse', 'DWT3D', 'IDWT3D', 'DTCWT1DForward', 'DTCWT1DInverse', 'DTCWT1D', 'IDTCWT1D',
            'WPT2DForward', 'WPT2DInverse', 'WPT2D', 'IWPT2D', 'wpt2d_freq_order', 'SWT1DForward', 'SWT1DInverse', 'SWT1D',
-           'ISWT1D']
+           'ISWT1D', 'WPT1DForward', 'WPT1DInverse', 'WPT1D', 'IWPT1D', 'wpt1d_freq_order']

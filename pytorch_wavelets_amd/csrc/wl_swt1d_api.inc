@@ -69,3 +69,4 @@ extern "C" int wl_swt1d_adjoint(const void* lo, const void* const* his, void* y,
         WL_SWT1D_BY_TAPS(WlSwt1dAdj, a, g, stream)
     });
 }
+#include "wl_wpt1d_api.inc"

@@ -1109,6 +1109,115 @@ def iwpt2d_level(y, filts, mode='zero', out_hw=None):
     return SFBWPT2D.apply(y, g0_row, g1_row, g0_col, g1_col, m, out_hw)
 
 
+# ---- the 1-D wavelet packet transform along the last axis (csrc/wl_wpt1d.h) ---------------------------------------------
+# `nlev` levels take (N, C, n) to the packed block (N, C, 2**nlev, n_nlev), band b = sum_j s_j 2**(nlev-j) (s_j = 1: the highpass
+# of level j); the next chunk of levels reads it as (N, 2**nlev C, n_nlev) - a view - so the band index of a J-level tree is the
+# binary number of its path, level 1 first.  Periodization with every level even and at least as long as the filter, even
+# L <= 20, not float64: one launch of the wave-tile kernels per (up to) three levels; everything else level by level on
+# ops.afb1d / ops.sfb1d with the band axis folded into the channels, with the same answer.
+def _wpt1d_analysis(x, h0, h1, mode, nlev):
+    """`nlev` (1..3) packet analysis levels of x (N, C, n), no autograd -> (N, C, 2**nlev, n_nlev)."""
+    y = ops.wpt1d_afb(x, h0, h1, mode, nlev) if ops.WPT1D_FUSED else None
+    if y is not None:
+        return y
+    N, C = x.shape[:2]
+    y = x
+    for j in range(nlev):
+        lo, hi = ops.afb1d(y, h0, h1, mode, 2)
+        y = torch.stack([lo, hi], 2).view(N, C << (j + 1), lo.shape[-1])         # channel c 2^j + b -> c 2^(j+1) + 2b + s
+    return y.view(N, C, 1 << nlev, y.shape[-1])
+
+
+def _wpt1d_synthesis(y, g0, g1, mode, nlev, out_len=None):
+    """`nlev` (1..3) packet synthesis levels of y (N, C, 2**nlev, m) -> (N, C, n): every level its natural length (2K,
+    or 2K - L + 2 outside periodization), or - out_len given - the lengths the analysis of out_len samples has on its way down."""
+    if y.dim() != 4 or y.shape[2] != 1 << nlev:
+        raise ValueError('%d packet level(s) take (N, C, %d, n) coefficients, not %s' % (nlev, 1 << nlev, tuple(y.shape)))
+    N, C, _, m = y.shape
+    x = None
+    if ops.WPT1D_FUSED and out_len in (None, m << nlev):
+        x = ops.wpt1d_sfb(y, g0, g1, mode, nlev)
+    if x is not None:
+        return x
+    lens = [None] * nlev
+    if out_len is not None:
+        lens[0] = out_len
+        for j in range(1, nlev):
+            lens[j] = ops.coeff_len(lens[j - 1], g0.numel(), mode)
+    for j in range(nlev, 0, -1):
+        y = y.reshape(N, C << (j - 1), 2, y.shape[-1])
+        y = ops.sfb1d(y[:, :, 0], y[:, :, 1], g0, g1, mode, 2, out_len=lens[j - 1])
+    return y
+
+
+class AFBWPT1D(Function):
+    """One to three levels of 1-D packet analysis.  ``AFBWPT1D.apply(x, h0, h1, mode_int, nlev) -> y (N,C,2**nlev,n')``; one level
+    = AFB1D's (x0, x1) as one packed block.  Backward = the packet synthesis with the same stored taps, every level cropped to
+    its input length (the reference's rule for AFB1D.backward, dwt/lowlevel.py:409-424)."""
+
+    @staticmethod
+    def forward(ctx, x, h0, h1, mode, nlev=1):
+        _check_bank_mode(mode)
+        ctx.save_for_backward(h0, h1)
+        ctx.geom = (x.shape[-1], mode, nlev)
+        return _wpt1d_analysis(x, h0, h1, mode, nlev)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        dx = None
+        if ctx.needs_input_grad[0]:
+            h0, h1 = ctx.saved_tensors
+            n, mode, nlev = ctx.geom
+            dx = _wpt1d_synthesis(dy, h0, h1, mode, nlev, out_len=n)
+        return dx, None, None, None, None
+
+
+class SFBWPT1D(Function):
+    """One to three levels of 1-D packet synthesis.  ``SFBWPT1D.apply(y (N,C,2**nlev,n'), g0, g1, mode_int, out_len, nlev) -> x``,
+    out_len = the length to crop to or None.  Backward = the packet analysis with the stored synthesis taps of dx at the length
+    it has (the reference's SFB1D.backward, dwt/lowlevel.py:729-743)."""
+
+    @staticmethod
+    def forward(ctx, y, g0, g1, mode, out_len, nlev=1):
+        _check_bank_mode(mode)
+        ctx.save_for_backward(g0, g1)
+        ctx.geom = (mode, nlev)
+        return _wpt1d_synthesis(y, g0, g1, mode, nlev, out_len=out_len)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dx):
+        dy = None
+        if ctx.needs_input_grad[0]:
+            g0, g1 = ctx.saved_tensors
+            dy = _wpt1d_analysis(dx, g0, g1, ctx.geom[0], ctx.geom[1])
+        return dy, None, None, None, None, None
+
+
+def wpt1d_level(x, h0, h1, mode='zero'):
+    """Function-level packet analysis of x (N, C, n) along n: (N, C, 2, n'), band 0 = lowpass.  Array-like filters are the
+    pywt-ordered ones (reversed here, as afb1d does); tensors are taken as prepared."""
+    if x.dim() != 3:
+        raise ValueError('a 1-D packet level takes (N, C, n) tensors, not %d-D ones' % x.dim())
+    return AFBWPT1D.apply(x, _as_taps(h0, x), _as_taps(h1, x), mode_to_int(mode))
+
+
+def iwpt1d_level(y, g0, g1, mode='zero', out_len=None):
+    """Function-level packet synthesis, the inverse of wpt1d_level: y (N, C, 2, n') -> (N, C, n), the natural length of a
+    synthesis level or out_len - a length whose analysis has n' coefficients.  Array-like filters are used as given (sfb1d)."""
+    def prep(g):
+        return g if isinstance(g, torch.Tensor) else torch.tensor(np.copy(np.array(g, dtype=np.float64).ravel()),
+                                                                  dtype=torch.float, device=y.device)
+    g0, g1 = prep(g0), prep(g1)
+    m = mode_to_int(mode)
+    if out_len is not None:
+        out_len = int(out_len)
+        if y.dim() == 4 and ops.coeff_len(out_len, g0.numel(), m) != y.shape[-1]:
+            raise ValueError('out_len %d has no %d coefficients' % (out_len, y.shape[-1]))
+    return SFBWPT1D.apply(y, g0, g1, m, out_len)
+
+
 # ---- the 3-D DWT: the 2-D engine on the N*C*D planes, then one depth level (csrc/wl_dwt3d.h) -------------------------
 # Sub-band s = 4 b_D + 2 b_W + b_H (b = 1: highpass) of a level: s = 0 is the low-pass, band s sits at yh[:, :, s - 1].  The 2-D
 # level's (ll, lh, hl, hh) = b_D-lowpass bands 0..3, so its dense outputs are the depth kernel's four sources as they are.

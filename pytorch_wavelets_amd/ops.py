@@ -1454,6 +1454,71 @@ def wpt2d_sfb(y, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, out_hw=None, nlev=1):
     return x
 
 
+# ---------------------------------------------------------------------------------------------- the 1-D wavelet packet transform
+WPT1D_FUSED = True   # up to three periodization levels of the packet tree per launch on the wave-tile kernels (csrc/wl_wpt1d.h).
+#                      False: everything level by level on afb1d / sfb1d, for A/B measurements and tests.
+WPT1D_TILE = 1024    # positions a wave holds: 64 lanes x WL_WPT1D_V of csrc/wl_wpt1d.h
+WPT1D_MAXJ = 3       # WL_WPT1D_MAXJ
+
+
+def wpt1d_core(L, J):
+    """Positions of a wave's tile that are stored after J packet levels of an L-tap bank, and what the tiles of a row advance
+    by (the seams of a row lie at multiples of it, minus `origin`): the tile less a halo of (L/2)(2^J - 1) positions, rounded
+    up to a multiple of 2^J, on either side."""
+    q = 2 ** J
+    return WPT1D_TILE - 2 * (((L // 2) * (q - 1) + q - 1) // q * q)
+
+
+def _wpt1d_covered(t, n, L, L1, mode, nlev):
+    """The envelope of wl_wpt1d_analysis / wl_wpt1d_synthesis for rows of n samples (include/wavelets_hip.h)."""
+    return not (t.dtype == torch.float64 or t.numel() == 0 or nlev < 1 or nlev > WPT1D_MAXJ or mode != 2 or L % 2 or L > 20
+                or L1 != L or n >= 1 << 30 or n % 2 ** nlev or n >> (nlev - 1) < L)
+
+
+def wpt1d_afb(x, h0, h1, mode, nlev, origin=0):
+    """`nlev` (1..3) levels of the periodized packet analysis along the LAST axis in ONE launch (wl_wpt1d_analysis):
+    x (..., n) -> y (..., 2**nlev, n / 2**nlev), band b = sum_j s_j 2**(nlev-j), s_j = 1 the highpass of level j.  None when the
+    launcher declines (another mode, n no multiple of 2**nlev, a last level shorter than the filter, float64, odd, long or
+    unequal filters): callers go level by level on afb1d.  `origin` (tests; a multiple of 2**nlev) moves the tile seams."""
+    _check_tensor(x, 'x')
+    L, n = h0.numel(), x.shape[-1]
+    if not _wpt1d_covered(x, n, L, h1.numel(), mode, nlev):
+        return None
+    rows = x.numel() // n
+    key = ('wpt1d_afb', x.device, x.dtype, rows, n, L, nlev)
+    if key in _FUSED_DECLINED:
+        return None
+    x = x.contiguous()
+    t0, t1 = _taps(h0, x), _taps(h1, x)
+    y = torch.empty(tuple(x.shape[:-1]) + (2 ** nlev, n >> nlev), dtype=x.dtype, device=x.device)
+    if _declined(key, 'wl_wpt1d_analysis', x, x.data_ptr(), y.data_ptr(), _DTYPES[x.dtype], rows, n, nlev, t0.data_ptr(),
+                 t1.data_ptr(), L, mode, int(origin), _stream(x)):
+        return None
+    return y
+
+
+def wpt1d_sfb(y, g0, g1, mode, nlev, origin=0):
+    """The transpose of wpt1d_afb in ONE launch (wl_wpt1d_synthesis): y (..., 2**nlev, m) -> x (..., 2**nlev * m) - the inverse
+    with the stored synthesis taps, the backward of the analysis with its own.  None when the launcher declines."""
+    _check_tensor(y, 'y')
+    if y.dim() < 2 or y.shape[-2] != 2 ** nlev:
+        raise ValueError('wpt1d_sfb: %s is no (..., 2**%d, m) tensor' % (tuple(y.shape), nlev))
+    L, n = g0.numel(), y.shape[-1] << nlev
+    if not _wpt1d_covered(y, n, L, g1.numel(), mode, nlev):
+        return None
+    rows = y.numel() // n
+    key = ('wpt1d_sfb', y.device, y.dtype, rows, n, L, nlev)
+    if key in _FUSED_DECLINED:
+        return None
+    y = y.contiguous()
+    t0, t1 = _taps(g0, y), _taps(g1, y)
+    x = torch.empty(tuple(y.shape[:-2]) + (n,), dtype=y.dtype, device=y.device)
+    if _declined(key, 'wl_wpt1d_synthesis', y, y.data_ptr(), x.data_ptr(), _DTYPES[y.dtype], rows, n, nlev, t0.data_ptr(),
+                 t1.data_ptr(), L, mode, int(origin), _stream(y)):
+        return None
+    return x
+
+
 # ---------------------------------------------------------------------------------------------- DTCWT
 def dtcwt_fwd1(x, h0, h1, mode, skip_hps=False):
     """Level-1 forward: x (N,C,H,W) -> ll (N,C,He,We), highs (N,C,6,He/2,We/2,2) or None."""
