@@ -137,6 +137,41 @@ WL_DEV void wl_dma4(const WlCtx& ctx, unsigned lds_off, const void* gsrc, bool l
     if (lane_on)
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off" : : "s"(m0), "v"(gsrc) : "memory", "m0");
 }
+// The same four copies with the non-temporal policy (`nt`): the line is marked for early eviction in L2 / the Infinity Cache - for
+// data a launch touches exactly once.  Which streams of which kernel take them is a measured, per-stream compile-time choice
+// (WL_ROWS_NT_LOAD and its kin); the LDS side, the counters and the waits are those of the plain forms.
+WL_DEV void wl_dma16_nt(const WlCtx& ctx, unsigned lds_off, const void* gsrc, bool lane_on) {
+    const unsigned m0 = __builtin_amdgcn_readfirstlane(ctx.lds_base + lds_off);
+    if (lane_on)
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt" : : "s"(m0), "v"(gsrc) : "memory", "m0");
+}
+WL_DEV void wl_dma16_s_nt(const WlCtx& ctx, unsigned lds_off, const void* sbase, unsigned voff, bool lane_on) {
+    const unsigned m0 = __builtin_amdgcn_readfirstlane(ctx.lds_base + lds_off);
+    if (lane_on)
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt" : : "s"(m0), "v"(voff), "s"(sbase) : "memory", "m0");
+}
+WL_DEV void wl_dma4_s_nt(const WlCtx& ctx, unsigned lds_off, const void* sbase, unsigned voff, bool lane_on) {
+    const unsigned m0 = __builtin_amdgcn_readfirstlane(ctx.lds_base + lds_off);
+    if (lane_on)
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2 nt" : : "s"(m0), "v"(voff), "s"(sbase) : "memory", "m0");
+}
+WL_DEV void wl_dma4_nt(const WlCtx& ctx, unsigned lds_off, const void* gsrc, bool lane_on) {
+    const unsigned m0 = __builtin_amdgcn_readfirstlane(ctx.lds_base + lds_off);
+    if (lane_on)
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off nt" : : "s"(m0), "v"(gsrc) : "memory", "m0");
+}
+// Stream stores: one element, or two adjacent ones in ONE access (8 bytes of float, 4 of float16 / bfloat16; p is aligned to
+// one element only), non-temporal.  The arithmetic and the bytes written are those of the plain stores they stand in for.
+template <typename T> WL_DEV void wl_stream_store(char* p, T v) {
+    typedef T V1 __attribute__((ext_vector_type(1), may_alias));
+    const V1 w = {v};
+    __builtin_nontemporal_store(w, reinterpret_cast<V1*>(p));
+}
+template <typename T> WL_DEV void wl_stream_store2(char* p, T a, T b) {
+    typedef T V2 __attribute__((ext_vector_type(2), aligned(sizeof(T)), may_alias));
+    const V2 w = {a, b};
+    __builtin_nontemporal_store(w, reinterpret_cast<V2*>(p));
+}
 template <int N> WL_DEV void wl_wait_vm() {
     static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
     __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));   // vmcnt(N), others untouched
@@ -148,6 +183,13 @@ void wl_dma16(const WlCtx& ctx, unsigned lds_off, const void* gsrc, bool lane_on
 void wl_dma4(const WlCtx& ctx, unsigned lds_off, const void* gsrc, bool lane_on);
 inline void wl_dma16_s(const WlCtx& ctx, unsigned lds_off, const void* sbase, unsigned voff, bool lane_on) { wl_dma16(ctx, lds_off, (const char*)sbase + voff, lane_on); }
 inline void wl_dma4_s(const WlCtx& ctx, unsigned lds_off, const void* sbase, unsigned voff, bool lane_on) { wl_dma4(ctx, lds_off, (const char*)sbase + voff, lane_on); }
+// (the host emulation has no cache policy: the non-temporal forms are the plain ones)
+inline void wl_dma16_nt(const WlCtx& ctx, unsigned lds_off, const void* gsrc, bool lane_on) { wl_dma16(ctx, lds_off, gsrc, lane_on); }
+inline void wl_dma4_nt(const WlCtx& ctx, unsigned lds_off, const void* gsrc, bool lane_on) { wl_dma4(ctx, lds_off, gsrc, lane_on); }
+inline void wl_dma16_s_nt(const WlCtx& ctx, unsigned lds_off, const void* sbase, unsigned voff, bool lane_on) { wl_dma16_s(ctx, lds_off, sbase, voff, lane_on); }
+inline void wl_dma4_s_nt(const WlCtx& ctx, unsigned lds_off, const void* sbase, unsigned voff, bool lane_on) { wl_dma4_s(ctx, lds_off, sbase, voff, lane_on); }
+template <typename T> inline void wl_stream_store(char* p, T v) { *reinterpret_cast<T*>(p) = v; }
+template <typename T> inline void wl_stream_store2(char* p, T a, T b) { T* q = reinterpret_cast<T*>(p); q[0] = a; q[1] = b; }
 void wl_emu_wait_vm(int n);
 template <int N> inline void wl_wait_vm() { wl_emu_wait_vm(N); }
 #endif

@@ -42,6 +42,24 @@
 #ifndef WL_ROWS_DEPTH
 #define WL_ROWS_DEPTH 3
 #endif
+// Cache policy of the kernel's two HBM streams, and the priority of its loader waves (1 = on): every byte is touched once per
+// launch.  Same-box A/Bs of the benchmark's step (WlAfbRows<float, 8, 2> then WlSfbRows<float, 8, 1>, 128x3x512x512, kernel
+// durations forward / inverse in us, profiles/r07_stream_policy_ab.json).  The two launches are NOT independent: what one leaves
+// in the Infinity Cache - lines to evict, dirty lines to write back - is paid by the next, so every switch moves time between the
+// two kernels.  A switch is judged on and off INSIDE the committed set (this one + WL_IROWS_NT_STORE): against the parent that
+// set takes the forward from 160.4 to 143.1 us and leaves the inverse where it was (168.9 -> 167.5).
+#ifndef WL_ROWS_NT_LOAD
+#define WL_ROWS_NT_LOAD 1       // loader: the LDS-DMA of the x rows.  Alone 160.4 / 168.9 -> 147.6 / 181.4 (what the forward gains the inverse
+                                // pays); with WL_IROWS_NT_STORE on: 150.4 / 171.3 without it -> 143.1 / 167.5 with it
+#endif
+#ifndef WL_ROWS_NT_STORE
+#define WL_ROWS_NT_STORE 0      // emit_row: the band stores and the last level's LL store (never the LDS ring writes).  Rejected:
+                                // 157.9 / 167.4 -> 206.6 / 146.6 and WRITE_SIZE 414 946 -> 458 633 KB (+10.5 %): the 259-float band rows
+                                // end in partial lines that leave L2 before the neighbouring wave has completed them
+#endif
+#ifndef WL_ROWS_LOADER_PRIO
+#define WL_ROWS_LOADER_PRIO 0   // run: s_setprio 3 for the loader waves, as in WlSfbRows.  No effect: 157.9 / 167.4 -> 159.0 / 166.9
+#endif
 
 // acc += tap * s.x  /  acc += tap * s.y  on (lo,hi) pairs: ONE v_pk_fma_f32, the broadcast half chosen by op_sel
 #if defined(__HIPCC__)
@@ -249,7 +267,8 @@ struct WlAfbRows {
 #pragma unroll
                 for (int p = 0; p < PPR; ++p) {
                     const int byte = (p * 64 + lane) * 16;
-                    wl_dma16(ctx, (unsigned)(slot + r * pitch + p * 1024), grow + byte, byte < row_bytes);
+                    if (WL_ROWS_NT_LOAD) wl_dma16_nt(ctx, (unsigned)(slot + r * pitch + p * 1024), grow + byte, byte < row_bytes);
+                    else wl_dma16(ctx, (unsigned)(slot + r * pitch + p * 1024), grow + byte, byte < row_bytes);
                 }
             }
         };
@@ -397,18 +416,23 @@ struct WlAfbRows {
         }
         cl = wl_v2{u.x, hi.x}; ch = wl_v2{u.y, hi.y};             // the lattice filters the (row-lo, row-hi) pair: a renaming of registers
     }
+    // one coefficient to HBM
+    static WL_DEV void put(char* p, T v) {
+        if (WL_ROWS_NT_STORE) wl_stream_store<T>(p, v);
+        else *reinterpret_cast<T*>(p) = v;
+    }
     template <bool LAST, bool HALO>
     static WL_DEV void emit_row(Lane& L, const Role& R, char* smem, wl_v2 cl, wl_v2 ch, int orow, bool keep) {
         const unsigned ob = L.ob;
         L.ob = ob + R.rowb;
         // keep: the row belongs to this segment (wave-uniform); halo rows of a cut plane are computed, not stored
         if (keep) {
-            *reinterpret_cast<T*>(R.hp0 + ob) = (T)cl.y;    // W-lo / H-hi
-            *reinterpret_cast<T*>(R.hp1 + ob) = (T)ch.x;    // W-hi / H-lo
-            *reinterpret_cast<T*>(R.hp2 + ob) = (T)ch.y;    // W-hi / H-hi
+            put(R.hp0 + ob, (T)cl.y);    // W-lo / H-hi
+            put(R.hp1 + ob, (T)ch.x);    // W-hi / H-lo
+            put(R.hp2 + ob, (T)ch.y);    // W-hi / H-hi
         }
         if (LAST) {
-            if (keep) *reinterpret_cast<T*>(R.llp + ((unsigned)orow * R.llrowb + R.kb)) = (T)cl.x;
+            if (keep) put(R.llp + ((unsigned)orow * R.llrowb + R.kb), (T)cl.x);
         } else {
             char* nrow = smem + (R.nring + (NP2 ? wl_uniform(wl_ring_slot(orow, R.rmask, R.nmagic)) : (orow & R.rmask)) * R.npitch);
             *reinterpret_cast<T*>(nrow + L.ndst) = (T)cl.x;
@@ -600,7 +624,12 @@ struct WlAfbRows {
         WlCtx cs = ctx;                                  // this wave's plane: its own part of the LDS
         cs.smem += sub * a.lds_plane; cs.lds_base += (unsigned)(sub * a.lds_plane);
         const int lev = plane < a.NC ? wl_uniform(a.role_level[wave]) : -2, col0 = wl_uniform(a.role_col0[wave]);   // (the last workgroup may hold fewer planes)
-        if (lev == -1) loader(a, sg, cs, plane, lane, col0);
+        if (lev == -1) {
+#if defined(__HIPCC__) && WL_ROWS_LOADER_PRIO
+            __builtin_amdgcn_s_setprio(3);   // its few instructions go first: every other wave waits for it at the barrier
+#endif
+            loader(a, sg, cs, plane, lane, col0);
+        }
         else if (lev == 0) compute<0>(a, sg, cs, plane, col0, lane);
         else if (lev == 1) compute<1>(a, sg, cs, plane, col0, lane);
         else if (lev == 2) compute<2>(a, sg, cs, plane, col0, lane);

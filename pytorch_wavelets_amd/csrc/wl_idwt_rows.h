@@ -39,6 +39,21 @@
 #define WL_ITICK() 0ull
 #endif
 #define WL_IROWS_CHUNK 1024     // bytes one LDS-DMA instruction moves: 64 lanes x 16 bytes
+// Cache policy of the kernel's two HBM streams (1 = non-temporal): every byte is touched once per launch.  Measured and judged
+// as described at WL_ROWS_NT_LOAD (wl_dwt_rows.h): kernel durations forward / inverse in us and the benchmark's step,
+// profiles/r07_stream_policy_ab.json (figures of one line are of one visit to one box; the boxes differ).
+#ifndef WL_IROWS_NT_LOAD
+#define WL_IROWS_NT_LOAD 0      // loader / loader_per: the LDS-DMA chunks of yl and yh[j], their dword tail pieces included.  Rejected
+                                // for its traffic: alone 157.9 / 167.4 -> 185.8 / 145.8, on top of the committed set 148.9 / 183.7 -> 142.9 / 180.8
+                                // (step 0.3424 -> 0.3309 ms), but FETCH_SIZE 212 634 -> 220 837 KB (+3.9 %; 1.038x the algorithmic bytes): the
+                                // 1 KiB chunks of the 4-byte aligned band planes straddle cache lines, and the shared line has left L2
+                                // before the next chunk reads its other half
+#endif
+#ifndef WL_IROWS_NT_STORE
+#define WL_IROWS_NT_STORE 1     // emit / emit_per: the level-0 stores of x (never the LDS ring writes): whole, aligned lines, nothing dirty
+                                // left behind for the next launch to write back.  Alone 160.4 / 168.9 -> 150.4 / 171.3; with WL_ROWS_NT_LOAD
+                                // on: 147.6 / 181.4 without it -> 143.1 / 167.5 with it
+#endif
 
 struct WlIRowsLevel {
     int Kh, Kw;         // coefficient rows / cols (size of yh[j]; the LL source is cropped to it)
@@ -147,6 +162,14 @@ struct WlSfbRows {
     static const int WARM = HL - 1;        // feeds that only fill the window
     static const int SZ = (int)sizeof(T);
 
+    static WL_DEV void dma16(const WlCtx& ctx, unsigned lds_off, const void* sbase, unsigned voff, bool lane_on) {
+        if (WL_IROWS_NT_LOAD) wl_dma16_s_nt(ctx, lds_off, sbase, voff, lane_on);
+        else wl_dma16_s(ctx, lds_off, sbase, voff, lane_on);
+    }
+    static WL_DEV void dma4(const WlCtx& ctx, unsigned lds_off, const void* sbase, unsigned voff, bool lane_on) {
+        if (WL_IROWS_NT_LOAD) wl_dma4_s_nt(ctx, lds_off, sbase, voff, lane_on);
+        else wl_dma4_s(ctx, lds_off, sbase, voff, lane_on);
+    }
     // ---- loader wave: sources [s0, s0+ns) of level j ---------------------------------------------------------------
     // A "step" = the next 1024-byte chunk of every source (one DMA instruction each, plus dword pieces where a plane ends
     // off a 16-byte boundary).  A step may go out once the rows it overwrites (the previous revolution's rows under the
@@ -190,8 +213,8 @@ struct WlSfbRows {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 if (i >= ns) break;
-                if (whole) wl_dma16_s(ctx, (unsigned)(dst[i] + rbyte), src[i], (unsigned)(pbyte + lane * 16), on);
-                if (tail) wl_dma4_s(ctx, (unsigned)(dst[i] + rbyte + (p16 - pbyte)), src[i], (unsigned)(p16 + lane * 4), lane < ptail);
+                if (whole) dma16(ctx, (unsigned)(dst[i] + rbyte), src[i], (unsigned)(pbyte + lane * 16), on);
+                if (tail) dma4(ctx, (unsigned)(dst[i] + rbyte + (p16 - pbyte)), src[i], (unsigned)(p16 + lane * 4), lane < ptail);
             }
             ++issued;
             rbyte += WL_IROWS_CHUNK; pbyte += WL_IROWS_CHUNK;
@@ -257,7 +280,7 @@ struct WlSfbRows {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     if (i >= ns) break;
-                    wl_dma16_s(ctx, (unsigned)dst[i] + slot, src[i], gro, lon);
+                    dma16(ctx, (unsigned)dst[i] + slot, src[i], gro, lon);
                 }
                 next += G;
                 return true;
@@ -272,9 +295,9 @@ struct WlSfbRows {
                 if (i >= ns) break;
                 for (int q = 0; q < nseg; ++q) {
                     const int byte = (q * 64 + lane) * 16;
-                    wl_dma16_s(ctx, (unsigned)dst[i] + slot + (unsigned)(q * WL_IROWS_CHUNK), src[i], gro + (unsigned)byte, byte + 16 <= rowb);
+                    dma16(ctx, (unsigned)dst[i] + slot + (unsigned)(q * WL_IROWS_CHUNK), src[i], gro + (unsigned)byte, byte + 16 <= rowb);
                 }
-                if (tail) wl_dma4_s(ctx, (unsigned)dst[i] + slot + (unsigned)rowb16, src[i], gro + (unsigned)(rowb16 + lane * 4), lane < tail);
+                if (tail) dma4(ctx, (unsigned)dst[i] + slot + (unsigned)rowb16, src[i], gro + (unsigned)(rowb16 + lane * 4), lane < tail);
             }
             ++next;
             return true;
@@ -407,6 +430,16 @@ struct WlSfbRows {
             wl_pk_fma_y(y1, R.gh1[LAT ? 0 : t], eb[OFF + HL - 1 - t]);
         }
     }
+    // one sample / one pair of adjacent samples of x to HBM
+    static WL_DEV void put1(char* p, T v) {
+        if (WL_IROWS_NT_STORE) wl_stream_store<T>(p, v);
+        else *reinterpret_cast<T*>(p) = v;
+    }
+    static WL_DEV void put2(char* p, T va, T vb) {
+        if (WL_IROWS_NT_STORE) { wl_stream_store2<T>(p, va, vb); return; }
+        T v[2] = {va, vb};
+        *reinterpret_cast<WlPairT*>(p) = *reinterpret_cast<WlPairT*>(v);
+    }
     // periodization: z rows m, m+1 (y0 = the two rows of z column 2q, y1 of column 2q+1) - level 0: to x, L/2 - 1 rows / columns earlier
     // (mod the plane, and by the segment's rotation); other levels: into the ring of the level below in z order, with the copies it wraps to
     template <int j>
@@ -420,12 +453,11 @@ struct WlSfbRows {
             char* p0 = R.yp + (unsigned)r0 * R.yrowb;
             char* p1 = R.yp + (unsigned)r1 * R.yrowb;
             if (!R.odd_wave) {
-                T v[2] = {(T)y0.x, (T)y1.x}, w[2] = {(T)y0.y, (T)y1.y};
-                *reinterpret_cast<WlPairT*>(p0 + R.ycol) = *reinterpret_cast<WlPairT*>(v);
-                *reinterpret_cast<WlPairT*>(p1 + R.ycol) = *reinterpret_cast<WlPairT*>(w);
+                put2(p0 + R.ycol, (T)y0.x, (T)y1.x);
+                put2(p1 + R.ycol, (T)y0.y, (T)y1.y);
             } else {   // the wave that holds the pair the roll splits between the row's last and first column
-                *reinterpret_cast<T*>(p0 + R.ycol) = (T)y0.x; *reinterpret_cast<T*>(p0 + R.ycol1) = (T)y1.x;
-                *reinterpret_cast<T*>(p1 + R.ycol) = (T)y0.y; *reinterpret_cast<T*>(p1 + R.ycol1) = (T)y1.y;
+                put1(p0 + R.ycol, (T)y0.x); put1(p0 + R.ycol1, (T)y1.x);
+                put1(p1 + R.ycol, (T)y0.y); put1(p1 + R.ycol1, (T)y1.y);
             }
         } else {
 #pragma unroll
@@ -457,13 +489,12 @@ struct WlSfbRows {
             char* r0 = R.yp + ((unsigned)m * R.yrowb + R.ycol);
             char* r1 = r0 + R.yrowb;
             if (!R.odd_wave) {
-                T v[2] = {(T)y0.x, (T)y1.x}, w[2] = {(T)y0.y, (T)y1.y};
-                *reinterpret_cast<WlPairT*>(r0) = *reinterpret_cast<WlPairT*>(v);
-                *reinterpret_cast<WlPairT*>(r1) = *reinterpret_cast<WlPairT*>(w);
+                put2(r0, (T)y0.x, (T)y1.x);
+                put2(r1, (T)y0.y, (T)y1.y);
             } else {   // the wave that holds the last pair of an odd-width row: that lane has one column only
-                *reinterpret_cast<T*>(r0) = (T)y0.x;
-                *reinterpret_cast<T*>(r1) = (T)y0.y;
-                if (R.two) { *reinterpret_cast<T*>(r0 + SZ) = (T)y1.x; *reinterpret_cast<T*>(r1 + SZ) = (T)y1.y; }
+                put1(r0, (T)y0.x);
+                put1(r1, (T)y0.y);
+                if (R.two) { put1(r0 + SZ, (T)y1.x); put1(r1 + SZ, (T)y1.y); }
             }
         } else {
             if (m < R.lrows) {
