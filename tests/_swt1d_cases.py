@@ -244,6 +244,35 @@ def check_two_byte(dev, wave, dtype):
         check_gradients(dev, wave, J, (2, 2, n), dtype)
 
 
+GRID_WAVES = tuple('db%d' % i for i in range(1, 11))        # L = 2, 4, .., 20: one case of the dispatchers' switch each
+GRID_DTYPES = (F32, F16, BF16)
+TNAME = {F32: 'float', F16: '_Float16', BF16: '__bf16'}
+
+
+def check_instantiation(dev, wave, dtype):
+    """WlSwt1dFwd<T, L> / WlSwt1dAdj<T, L> of one tap count and element type x nlev 1..3 through ops.swt1d_fwd / swt1d_adj: three
+    rows of one tile plus one position, which crosses the seam.  The kernel names are built from (T, L)."""
+    L = ntaps(wave)
+    h = ana_taps(wave)
+    for nlev in (1, 2, 3):
+        n = ops.swt1d_core(L, nlev) + 1
+        xn, cl, ch, _ = _inputs((3, n), nlev, 21)
+        th = [dev_t(t, F32, dev) for t in h]
+        x, tl, ths = dev_t(xn, dtype, dev), dev_t(cl, dtype, dev), [dev_t(v, dtype, dev) for v in ch]
+        c0 = pw.launch_count()
+        lo, his = ops.swt1d_fwd(x, th[0], th[1], nlev)
+        y = ops.swt1d_adj(tl, ths, th[0], th[1], 0.5)
+        ks = pw.kernels_since(c0)
+        assert ks == ['WlSwt1d%s<%s, %d>' % (k, TNAME[dtype], L) for k in ('Fwd', 'Adj')], ks
+        what = '%s nlev=%d %s' % (wave, nlev, dtype)
+        rl, rh = analysis_ref(npy(x), h, nlev)
+        floor = cancel_floor(h, npy(x), *[analysis_ref(npy(x), h, j)[0] for j in range(1, nlev)])
+        close(lo, rl, dtype, 'lo ' + what)
+        for j in range(nlev):
+            close(his[j], rh[j], dtype, 'hi[%d] %s' % (j, what), floor=floor)
+        close(y, adjoint_ref(npy(tl), [npy(v) for v in ths], h, 0.5), dtype, 'adjoint ' + what)
+
+
 def fused_pair(dev, wave, J, shape, dtype, origin):
     """(lo, his, y): ops.swt1d_fwd of x and ops.swt1d_adj of random bands, the first tile moved left by `origin`."""
     xn, cl, ch, _ = _inputs(shape, J, 13)

@@ -129,6 +129,13 @@ def _below(n):
     return grid
 
 
+def _exactly(n):
+    def grid(g):
+        return g == n
+    grid.__name__ = 'grid == %d' % n
+    return grid
+
+
 def _tail(kernel, tail):
     """`kernel<..., tail>`: the trailing template arguments."""
     def pred(k):
@@ -374,6 +381,12 @@ CASES = [
     ('dwt1d_fused', lambda: E.check_dwt1d_fused('cpu', cases=[('db4', 'symmetric', 3, (2, 2, 3000), F32), ('db2', 'periodization', 2, (1, 2, 1000), F32)]),
      [_t('WlDwt1dFused'), _t('WlIdwt1dFused')]),
     ('small_planes', lambda: _dwt_fwd_inv('db2', 'symmetric', (3, 2, 20, 24), 2), [_t('WlAfbSmall'), _t('WlSfbSmall')]),
+    # the LDS reuse between a workgroup's consecutive units: 14 rows of three chunks on the 2-CU chip = two consecutive chunks per
+    # workgroup (28 workgroups for 42 chunks: the commit of chunk c + 1 into buffer 0 follows the levels of chunk c); 36 planes =
+    # nine groups of four on the eight resident workgroups (workgroup 0 walks over groups 0 and 8)
+    ('dwt1d_chunk_walk', lambda: E.check_dwt1d_fused('cpu', cases=[('db4', 'symmetric', 1, (14, 1, 8400), F32)]),
+     [_t('WlDwt1dFused', grid=_exactly(28)), _t('WlIdwt1dFused')]),
+    ('small_planes_group_walk', lambda: _dwt_fwd_inv('db2', 'symmetric', (9, 4, 32, 32), 2), [_t('WlAfbSmall', grid=_exactly(8)), _t('WlSfbSmall')]),
     ('dt_small', lambda: _dtcwt_fwd_inv((6, 3, 32, 32), 'near_sym_a', 'qshift_a', 1, stream=False), [_t('WlDtFwd1Small')]),
     ('rot_level1', lambda: [E.check_rot(n, 'cpu', F32, 1e-5) for n in E.ROT_CASES[:1]], [_t('WlDtFwd1Rot')]),
     ('swt', lambda: [E.check_swt(n, 'cpu', F32, 1e-5) for n in E.SWT_CASES[:1]], [_t('WlSwtLevel')]),
