@@ -157,4 +157,4 @@ extern "C" int wl_dtcwt1d_synthesis(const void* lo, int n_lo, const void* const*
         }
     });
 }
-#include "wl_swt1d_api.inc"
+#include "wl_wave1d_api.inc"

@@ -1,0 +1,130 @@
+// C ABI of the wave-tile kernels (wl_wave1d.h): the 1-D stationary transform (wl_swt1d.h) and the 1-D wavelet packet transform
+// (wl_wpt1d.h).  Included at the end of wl_dtcwt1d_api.inc, so compiled in the fourth translation unit of the HIP build
+// (wl_dtinv_hip.hip) and in the matching unit of the host emulation.
+#include "wl_api_common.h"
+#include "wl_swt1d.h"
+#include "wl_wpt1d.h"
+
+// the grid of a launch: tiles of `core` positions from -origin on, WL_WAVE1D_WAVES tiles per workgroup
+struct WlWave1dGrid { int core, tiles; int64_t waves, nblocks; };
+
+// The checks every entry starts with (their order decides which code wins when several fail); `family_ok`: the transform's own
+// mode / extension test, which answers with the same code as the level and tap limits.
+static int wl_wave1d_check(int64_t rows, int len, int J, int L, int dtype, bool family_ok, int origin) {
+    if (rows < 0 || len < 1 || J < 1 || L < 1 || origin < 0) return WL_ERR_SHAPE;
+    if (dtype != WL_F32 && dtype != WL_F16 && dtype != WL_BF16) return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
+    if (J > WL_WAVE1D_MAXJ || (L & 1) || L > WL_WAVE1D_MAXL || !family_ok || len >= (1 << 30)) return WL_ERR_UNSUPPORTED;
+    return 0;
+}
+
+// ... and end with, once the transform has worked out its core
+static int wl_wave1d_grid(int64_t rows, int len, int origin, int core, WlWave1dGrid& g) {
+    if (origin >= core) return WL_ERR_SHAPE;
+    g.core = core;
+    g.tiles = wl_cdiv(len + origin, core);
+    g.waves = rows * g.tiles;
+    g.nblocks = wl_cdiv64(g.waves, WL_WAVE1D_WAVES);
+    return 0;
+}
+
+static int wl_swt1d_grid(int64_t rows, int N, int J, int L, int dtype, int ext, int origin, WlWave1dGrid& g) {
+    const int rc = wl_wave1d_check(rows, N, J, L, dtype, ext == WL_EXT_PERIODIC, origin);
+    if (rc != 0) return rc;
+    return wl_wave1d_grid(rows, N, origin, 64 * WL_WAVE1D_V - (L - 1) * ((1 << J) - 1), g);
+}
+
+// `head`: the halo in front of each core
+static int wl_wpt1d_grid(int64_t rows, int len, int nlev, int L, int dtype, int mode, int origin, int& head, WlWave1dGrid& g) {
+    const int rc = wl_wave1d_check(rows, len, nlev, L, dtype, mode == 2, origin);
+    if (rc != 0) return rc;
+    const int q = 1 << nlev;
+    // every level's band is even and at least as long as the filter (shorter: the reference's single fold is not the circular form)
+    if (len % q != 0 || (len >> (nlev - 1)) < L) return WL_ERR_UNSUPPORTED;
+    head = ((L / 2) * (q - 1) + q - 1) / q * q;
+    if (origin % q != 0) return WL_ERR_SHAPE;
+    return wl_wave1d_grid(rows, len, origin, 64 * WL_WAVE1D_V - 2 * head, g);
+}
+
+// the fields every argument struct has
+#define WL_WAVE1D_FILL(a, g, nrows, n, J, org) \
+    a.rows = nrows; a.waves = g.waves; a.len = n; a.nlev = J; a.tiles = g.tiles; a.core = g.core; a.origin = org
+
+#define WL_WAVE1D_BY_TAPS(K, a, g, stream)                                                     \
+    switch (L) {                                                                               \
+        case 2: return wl_launch<K<T, 2> >(a, g.nblocks, 0, stream);                           \
+        case 4: return wl_launch<K<T, 4> >(a, g.nblocks, 0, stream);                           \
+        case 6: return wl_launch<K<T, 6> >(a, g.nblocks, 0, stream);                           \
+        case 8: return wl_launch<K<T, 8> >(a, g.nblocks, 0, stream);                           \
+        case 10: return wl_launch<K<T, 10> >(a, g.nblocks, 0, stream);                         \
+        case 12: return wl_launch<K<T, 12> >(a, g.nblocks, 0, stream);                         \
+        case 14: return wl_launch<K<T, 14> >(a, g.nblocks, 0, stream);                         \
+        case 16: return wl_launch<K<T, 16> >(a, g.nblocks, 0, stream);                         \
+        case 18: return wl_launch<K<T, 18> >(a, g.nblocks, 0, stream);                         \
+        default: return wl_launch<K<T, 20> >(a, g.nblocks, 0, stream);                         \
+    }
+
+extern "C" int wl_swt1d_analysis(const void* x, void* lo, void* const* his, int dtype, int64_t rows, int N, int J, const void* h0,
+                                 const void* h1, int L, int ext, double scale, int origin, void* stream) {
+    WlWave1dGrid g;
+    const int rc = wl_swt1d_grid(rows, N, J, L, dtype, ext, origin, g);
+    if (rc != 0) return rc;
+    if (!x || !lo || !his) return WL_ERR_SHAPE;
+    if (!h0 || !h1) return WL_ERR_TAPS;
+    if (rows == 0) return 0;
+    WL_DISPATCH_FLOAT(dtype, {
+        WlSwt1dFwdArgs<T> a;
+        a.x = (const T*)x; a.lo = (T*)lo;
+        for (int l = 0; l < WL_WAVE1D_MAXJ; ++l) a.hi[l] = l < J ? (T*)his[l] : nullptr;
+        a.h0 = (const float*)h0; a.h1 = (const float*)h1;
+        WL_WAVE1D_FILL(a, g, rows, N, J, origin);
+        a.scale = (float)scale;
+        WL_WAVE1D_BY_TAPS(WlSwt1dFwd, a, g, stream)
+    });
+}
+
+extern "C" int wl_swt1d_adjoint(const void* lo, const void* const* his, void* y, int dtype, int64_t rows, int N, int J, const void* g0,
+                                const void* g1, int L, int ext, double scale, int origin, void* stream) {
+    WlWave1dGrid g;
+    const int rc = wl_swt1d_grid(rows, N, J, L, dtype, ext, origin, g);
+    if (rc != 0) return rc;
+    if (!lo || !y || !his) return WL_ERR_SHAPE;
+    if (!g0 || !g1) return WL_ERR_TAPS;
+    if (rows == 0) return 0;
+    WL_DISPATCH_FLOAT(dtype, {
+        WlSwt1dAdjArgs<T> a;
+        a.lo = (const T*)lo; a.y = (T*)y;
+        for (int l = 0; l < WL_WAVE1D_MAXJ; ++l) a.hi[l] = l < J ? (const T*)his[l] : nullptr;
+        a.g0 = (const float*)g0; a.g1 = (const float*)g1;
+        WL_WAVE1D_FILL(a, g, rows, N, J, origin);
+        a.scale = (float)scale;
+        WL_WAVE1D_BY_TAPS(WlSwt1dAdj, a, g, stream)
+    });
+}
+
+#define WL_WPT1D_ENTRY(K, from, to, t0, t1)                                                                                     \
+    WlWave1dGrid g;                                                                                                             \
+    int head;                                                                                                                   \
+    const int rc = wl_wpt1d_grid(rows, len, nlev, L, dtype, mode, origin, head, g);                                             \
+    if (rc != 0) return rc;                                                                                                     \
+    if (!from || !to) return WL_ERR_SHAPE;                                                                                      \
+    if (!t0 || !t1) return WL_ERR_TAPS;                                                                                         \
+    if (rows == 0) return 0;                                                                                                    \
+    WL_DISPATCH_FLOAT(dtype, {                                                                                                  \
+        WlWpt1dArgs<T> a;                                                                                                       \
+        a.src = (const T*)from; a.dst = (T*)to;                                                                                 \
+        a.f0 = (const float*)t0; a.f1 = (const float*)t1;                                                                       \
+        WL_WAVE1D_FILL(a, g, rows, len, nlev, origin);                                                                          \
+        a.head = head;                                                                                                          \
+        WL_WAVE1D_BY_TAPS(K, a, g, stream)                                                                                      \
+    })
+
+extern "C" int wl_wpt1d_analysis(const void* x, void* y, int dtype, int64_t rows, int len, int nlev, const void* h0, const void* h1,
+                                 int L, int mode, int origin, void* stream) {
+    WL_WPT1D_ENTRY(WlWpt1dAfb, x, y, h0, h1);
+}
+
+extern "C" int wl_wpt1d_synthesis(const void* y, void* x, int dtype, int64_t rows, int len, int nlev, const void* g0, const void* g1,
+                                  int L, int mode, int origin, void* stream) {
+    WL_WPT1D_ENTRY(WlWpt1dSfb, y, x, g0, g1);
+}
+#undef WL_WPT1D_ENTRY

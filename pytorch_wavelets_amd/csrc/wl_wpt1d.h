@@ -1,112 +1,27 @@
 // The 1-D wavelet packet transform (the full tree: every band is split again) along the last axis, periodization, up to three
-// levels per launch, on wave tiles in the manner of wl_swt1d.h: no LDS, no workgroup barrier, no role split.
+// levels per launch, on the wave tiles of wl_wave1d.h (the tile scheme, the piece accesses and the fetch are explained there).
 //
 //   * rows of a (rows, len) tensor go to / come from the packed (rows, 2^J, len / 2^J) tensor of the J levels of a launch: band b
 //     of a row - b = sum_j s_j 2^(J-j), s_j = 1 the highpass taken at level j, level 1 the most significant bit - is one
 //     contiguous run of len / 2^J coefficients, so the next launch reads the bands as 2^J times as many rows;
-//   * a WAVE owns a tile of 64 * V consecutive UNFOLDED positions of one row: position p is sample p mod len (a true floor-mod:
-//     tiles start left of 0, and a row may wrap many times inside one tile).  len is a multiple of 2^J, so every level of the
-//     periodized tree is periodic on the unfolded coordinates and no level has boundary logic;
-//   * lane l holds positions a + l*V .. a + l*V + V - 1 in registers, as float; after level j it holds V / 2^j consecutive
-//     coefficients of each of the 2^j bands - V registers at every level.  With VJ coefficients of a band per lane, the source at
-//     band-relative offset M of a lane is register M mod VJ of lane l + floor(M / VJ), both compile-time: the lane's own
-//     register or one wl_shfl.  The sources of a band are walked in ascending M, each fetched ONCE and used by every
-//     (output, tap) pair that wants it: (L - 2) shuffled values per lane and band split, (L - 2)(2^J - 1) per launch;
-//   * the sum of an output runs over its sources in ascending M (analysis: taps ascending; synthesis: the lowpass term in front
-//     of the highpass term), every term an explicit fused multiply-add: an output's bits do not depend on where in a tile, or
-//     in which tile, it falls.  Intermediate levels stay fp32 in registers, the last level rounds once per store;
-//   * a level eats at most L/2 positions of its own resolution on either side; lanes near the tile's ends compute garbage (their
-//     shuffles wrap around the wave) that is never stored.  head = (L/2)(2^J - 1) rounded up to a multiple of 2^J covers all J
-//     levels in both directions, the CORE of a tile is the 64 * V - 2 * head positions in between.  Tile starts and the core
-//     are multiples of 2^J, so every lane decimates on the row's own phase.  Only the core is stored, tiles advance by the core,
-//     the grid is rows x tiles, one tile per wave, WL_WPT1D_WAVES waves per workgroup.  A wave whose tile index is past the
-//     grid leaves as a whole; inside the body all 64 lanes reach every shuffle;
-//   * the row side moves in 16-byte pieces of ELEMENT alignment (wl_swt1d.h) where a piece lies inside the row (stores: inside
-//     the core), element by element at the wrap and at the core's ends.  On the band side a lane owns V / 2^J consecutive
-//     coefficients of a band: its piece is 16 bytes where it owns that much and its whole run (8 or 4 bytes) where it owns
-//     less - consecutive lanes touch consecutive addresses, a band of a tile is one contiguous run of core / 2^J elements.
+//   * len is a multiple of 2^J, so every level of the periodized tree is periodic on the unfolded coordinates.  After level j a
+//     lane holds V / 2^j consecutive coefficients of each of the 2^j bands - V registers at every level - and fetches a
+//     band's sources from that band's run of registers: (L - 2) shuffled values per lane and band split, (L - 2)(2^J - 1) per
+//     launch.  Synthesis sums the lowpass term in front of the highpass term; the last level rounds once per store;
+//   * a level eats at most L/2 positions of its own resolution on either side.  head = (L/2)(2^J - 1) rounded up to a multiple
+//     of 2^J covers all J levels in both directions, the core is the 64 * V - 2 * head positions in between.  Tile starts and
+//     the core are multiples of 2^J, so every lane decimates on the row's own phase (and `origin` is a multiple of 2^J);
+//   * on the band side a lane owns V / 2^J consecutive coefficients of a band: its piece is 16 bytes where it owns that much
+//     and its whole run (8 or 4 bytes) where it owns less - consecutive lanes touch consecutive addresses, a band of a tile
+//     is one contiguous run of core / 2^J elements.
 //
 //   analysis of a band of even length m:   lo[k], hi[k] = sum_t h0[t], h1[t] * in[(2k + t - (L/2 - 1)) mod m]
 //   synthesis, its exact transpose:        out[i] = sum over (k, t) with 2k + t - (L/2 - 1) = i (mod m) of g0[t] lo[k] + g1[t] hi[k]
 // (the periodization bank of wl_corr1d / wl_synth1d with the stored taps, for bands at least as long as the filter).  The two
 // kernels serve four directions: the transform (analysis taps), its backward (synthesis kernel, analysis taps), the inverse
 // (synthesis taps) and the inverse's backward (analysis kernel, synthesis taps).
-// `origin` (tests; a multiple of 2^J) moves the first tile's core left by that many positions: the seams fall elsewhere, the
-// bits stay.
 #pragma once
-#include <utility>
-#include "wl_common.h"
-
-#define WL_WPT1D_MAXJ 3
-#define WL_WPT1D_MAXL 20
-#define WL_WPT1D_WAVES 4       // tiles (waves) per workgroup
-#define WL_WPT1D_V 16          // positions per lane
-
-// E elements as one access of element alignment (a struct of elements is taken apart into element accesses)
-template <typename T, int E> struct WlWptPiece;
-#define WL_WPT_PIECE(T, E) \
-    template <> struct WlWptPiece<T, E> { typedef T type __attribute__((ext_vector_type(E), aligned(sizeof(T)), may_alias)); };
-WL_WPT_PIECE(float, 2) WL_WPT_PIECE(float, 4)
-WL_WPT_PIECE(wl_half, 2) WL_WPT_PIECE(wl_half, 4) WL_WPT_PIECE(wl_half, 8)
-WL_WPT_PIECE(wl_bf16, 2) WL_WPT_PIECE(wl_bf16, 4) WL_WPT_PIECE(wl_bf16, 8)
-#undef WL_WPT_PIECE
-
-// elements of a lane's piece: 16 bytes, or all N where N elements are less than that
-template <typename T, int N> struct WlWptRun { static const int E = N * (int)sizeof(T) < 16 ? N : 16 / (int)sizeof(T); };
-
-// N consecutive unfolded positions of a periodic run of `len` elements, the first one element s0 (0 <= s0 < len), into
-// r[off .. off + N)
-template <typename T, int N, int V>
-WL_DEV void wl_wpt1d_load(const T* run, int s0, int len, float (&r)[V], int off) {
-    constexpr int E = WlWptRun<T, N>::E;
-    static_assert(N % E == 0, "a lane holds whole pieces");
-#pragma unroll
-    for (int k = 0; k < N; k += E) {
-        int s = s0 + k;
-        if (s >= len) s %= len;
-        if (s + E <= len) {
-            const typename WlWptPiece<T, E>::type v = *reinterpret_cast<const typename WlWptPiece<T, E>::type*>(run + s);
-#pragma unroll
-            for (int e = 0; e < E; ++e) r[off + k + e] = (float)v[e];
-        } else {
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                r[off + k + e] = (float)run[s];
-                s = s + 1 == len ? 0 : s + 1;
-            }
-        }
-    }
-}
-
-// positions p0 .. p0 + N - 1 of a lane, held in r[off .. off + N): those inside [c0, c1) (0 <= c0, c1 <= len: positions that
-// are elements of the run) are stored
-template <typename T, int N, int V>
-WL_DEV void wl_wpt1d_store(T* run, int p0, int c0, int c1, const float (&r)[V], int off) {
-    constexpr int E = WlWptRun<T, N>::E;
-#pragma unroll
-    for (int k = 0; k < N; k += E) {
-        const int p = p0 + k;
-        if (p >= c0 && p + E <= c1) {
-            typename WlWptPiece<T, E>::type v;
-#pragma unroll
-            for (int e = 0; e < E; ++e) v[e] = (T)r[off + k + e];
-            *reinterpret_cast<typename WlWptPiece<T, E>::type*>(run + p) = v;
-        } else {
-#pragma unroll
-            for (int e = 0; e < E; ++e)
-                if (p + e >= c0 && p + e < c1) run[p + e] = (T)r[off + k + e];
-        }
-    }
-}
-
-// band-relative source M of a lane that holds VJ coefficients of the band in in[O .. O + VJ): register M mod VJ of lane
-// + floor(M / VJ), fetched once
-template <int V, int VJ, int O, int M>
-WL_DEV float wl_wpt1d_fetch(const float (&in)[V], int lane) {
-    constexpr int Q = (M >= 0 ? M : M - VJ + 1) / VJ, K = M - Q * VJ;
-    if constexpr (Q == 0) return in[O + K];
-    else return wl_shfl(in[O + K], lane + Q);
-}
+#include "wl_wave1d.h"
 
 // One analysis level on the lane's V registers: V / VI bands of VI coefficients each; band B's lowpass becomes band 2B, its
 // highpass band 2B + 1, VI / 2 coefficients each.  Per band the sources M = 2k + t - (L/2 - 1) in ascending order.
@@ -117,7 +32,7 @@ struct WlWpt1dAfbLevel {
     template <int S>
     static WL_DEV void step(const float (&in)[V], const float (&h0)[L], const float (&h1)[L], int lane, float (&out)[V]) {
         constexpr int B = S / NM, M = LO + S % NM;
-        const float v = wl_wpt1d_fetch<V, VI, B * VI, M>(in, lane);
+        const float v = wl_wave1d_fetch<V, VI, B * VI, M>(in, lane);
 #pragma unroll
         for (int k = 0; k < VO; ++k) {
             const int t = M - 2 * k + (L / 2 - 1);
@@ -148,8 +63,8 @@ struct WlWpt1dSfbLevel {
     template <int S>
     static WL_DEV void step(const float (&in)[V], const float (&g0)[L], const float (&g1)[L], int lane, float (&out)[V]) {
         constexpr int B = S / NM, M = LO + S % NM;
-        const float vl = wl_wpt1d_fetch<V, VC, B * VX, M>(in, lane);
-        const float vh = wl_wpt1d_fetch<V, VC, B * VX + VC, M>(in, lane);
+        const float vl = wl_wave1d_fetch<V, VC, B * VX, M>(in, lane);
+        const float vh = wl_wave1d_fetch<V, VC, B * VX + VC, M>(in, lane);
 #pragma unroll
         for (int i = 0; i < VX; ++i) {
             const int t = i + (L / 2 - 1) - 2 * M;
@@ -180,58 +95,51 @@ struct WlWpt1dArgs {
     int len, nlev, tiles, head, core, origin;
 };
 
-// what both kernels make of their wave: row, first position of the lane, the core cut to the row
-struct WlWpt1dTile { int64_t base; int lane, p0, c0, c1; };
-
-template <typename T, int V>
-WL_DEV bool wl_wpt1d_tile(const WlWpt1dArgs<T>& a, const WlCtx& ctx, WlWpt1dTile& t) {
-    const int64_t w = ctx.bid * WL_WPT1D_WAVES + (ctx.tid >> 6);
-    if (w >= a.waves) return false;                    // (the wave as a whole)
-    t.lane = ctx.tid & 63;
-    const int64_t row = w / a.tiles;
-    const int tile = (int)(w - row * a.tiles);
-    const int cs = tile * a.core - a.origin;           // the core: [cs, cs + core) cut to the row
-    t.c0 = cs > 0 ? cs : 0;
-    t.c1 = cs + a.core < a.len ? cs + a.core : a.len;
-    t.p0 = cs - a.head + t.lane * V;
-    t.base = row * a.len;
+// The tile of the wave; false: the wave is past the grid and leaves (as a whole).  Both kernels take the test through this
+// function and the stationary kernels write it into their bodies: either family compiled the other's way gets other
+// registers ("One tile function, two exits").
+template <int V, typename T>
+WL_DEV bool wl_wpt1d_tile(const WlWpt1dArgs<T>& a, const WlCtx& ctx, WlWave1dTile& t) {
+    const int64_t w = wl_wave1d_wave(ctx);
+    if (w >= a.waves) return false;
+    wl_wave1d_tile<V>(a, ctx, w, a.head, t);
     return true;
 }
 
 // the 2^NL bands of the lane, V >> NL coefficients each, to / from the packed side
 template <typename T, int V, int NL>
-WL_DEV void wl_wpt1d_store_bands(T* y, const WlWpt1dTile& t, int len, const float (&r)[V]) {
+WL_DEV void wl_wpt1d_store_bands(T* y, const WlWave1dTile& t, int len, const float (&r)[V]) {
     constexpr int VJ = V >> NL;
     const int m = len >> NL;
 #pragma unroll
     for (int b = 0; b < (1 << NL); ++b)
-        wl_wpt1d_store<T, VJ, V>(y + t.base + (int64_t)b * m, t.p0 >> NL, t.c0 >> NL, t.c1 >> NL, r, b * VJ);
+        wl_wave1d_store<T, VJ, V>(y + t.base + (int64_t)b * m, t.p0 >> NL, t.c0 >> NL, t.c1 >> NL, r, b * VJ);
 }
 
 template <typename T, int V, int NL>
-WL_DEV void wl_wpt1d_load_bands(const T* y, const WlWpt1dTile& t, int len, float (&r)[V]) {
+WL_DEV void wl_wpt1d_load_bands(const T* y, const WlWave1dTile& t, int len, float (&r)[V]) {
     constexpr int VJ = V >> NL;
     const int m = len >> NL;
     const int s0 = wl_pmod(t.p0 >> NL, m);             // (p0 is a multiple of 2^NL: the shift is exact)
 #pragma unroll
     for (int b = 0; b < (1 << NL); ++b)
-        wl_wpt1d_load<T, VJ, V>(y + t.base + (int64_t)b * m, s0, m, r, b * VJ);
+        wl_wave1d_load<T, VJ, V>(y + t.base + (int64_t)b * m, s0, m, r, b * VJ);
 }
 
 template <typename T, int L>
 struct WlWpt1dAfb {
     typedef WlWpt1dArgs<T> Args;
-    static const int kThreads = 64 * WL_WPT1D_WAVES;
+    static const int kThreads = 64 * WL_WAVE1D_WAVES;
     static const int kMinWaves = 2;
-    static const int V = WL_WPT1D_V;
+    static const int V = WL_WAVE1D_V;
     static WL_DEV void run(const Args& a, const WlCtx& ctx) {
-        WlWpt1dTile t;
-        if (!wl_wpt1d_tile<T, V>(a, ctx, t)) return;
+        WlWave1dTile t;
+        if (!wl_wpt1d_tile<V>(a, ctx, t)) return;
         float h0[L], h1[L];
 #pragma unroll
         for (int i = 0; i < L; ++i) { h0[i] = a.f0[i]; h1[i] = a.f1[i]; }
         float r[V], s[V];
-        wl_wpt1d_load<T, V, V>(a.src + t.base, wl_pmod(t.p0, a.len), a.len, r, 0);
+        wl_wave1d_load<T, V, V>(a.src + t.base, wl_pmod(t.p0, a.len), a.len, r, 0);
         WlWpt1dAfbLevel<L, V, V>::run(r, h0, h1, t.lane, s);
         if (a.nlev == 1) {
             wl_wpt1d_store_bands<T, V, 1>(a.dst, t, a.len, s);
@@ -250,12 +158,12 @@ struct WlWpt1dAfb {
 template <typename T, int L>
 struct WlWpt1dSfb {
     typedef WlWpt1dArgs<T> Args;
-    static const int kThreads = 64 * WL_WPT1D_WAVES;
+    static const int kThreads = 64 * WL_WAVE1D_WAVES;
     static const int kMinWaves = 2;
-    static const int V = WL_WPT1D_V;
+    static const int V = WL_WAVE1D_V;
     static WL_DEV void run(const Args& a, const WlCtx& ctx) {
-        WlWpt1dTile t;
-        if (!wl_wpt1d_tile<T, V>(a, ctx, t)) return;
+        WlWave1dTile t;
+        if (!wl_wpt1d_tile<V>(a, ctx, t)) return;
         float g0[L], g1[L];
 #pragma unroll
         for (int i = 0; i < L; ++i) { g0[i] = a.f0[i]; g1[i] = a.f1[i]; }
@@ -271,6 +179,6 @@ struct WlWpt1dSfb {
             wl_wpt1d_load_bands<T, V, 1>(a.src, t, a.len, s);
         }
         WlWpt1dSfbLevel<L, V, V / 2>::run(s, g0, g1, t.lane, r);
-        wl_wpt1d_store<T, V, V>(a.dst + t.base, t.p0, t.c0, t.c1, r, 0);
+        wl_wave1d_store<T, V, V>(a.dst + t.base, t.p0, t.c0, t.c1, r, 0);
     }
 };

@@ -667,7 +667,7 @@ def sfb1d_atrous(lo, hi, g0, g1, mode='periodic', dim=-1, dilation=1):
 # three levels are ONE launch of the wave-tile kernels (csrc/wl_swt1d.h: x read once, the intermediate lowpasses stay fp32 in
 # registers); deeper levels and everything else go level by level on corr1d / corr1d_adj, with the same answer.
 def _swt1d_fused_levels(t, L, ext, J):
-    if not ops.SWT1D_FUSED or ext != ops.EXT_PERIODIC or t.dtype == torch.float64 or L % 2 or L > 20:
+    if not ops.SWT1D_FUSED or ext != ops.EXT_PERIODIC or not ops.wave1d_covered(t.dtype, L):
         return 0
     return min(J, ops.SWT1D_MAXJ)
 

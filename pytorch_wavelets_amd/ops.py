@@ -1318,22 +1318,36 @@ def dtcwt1d_inv(lo, his, ns, rules, out_len, taps, qstart, chunk=None):
     return y
 
 
+# ---------------------------------------------------------------------------------------------- wave tiles
+# (csrc/wl_wave1d.h): what the launchers of the 1-D stationary and the 1-D wavelet packet transform share
+WAVE1D_TILE = 1024   # positions a wave holds: 64 lanes x WL_WAVE1D_V
+WAVE1D_MAXJ = 3      # WL_WAVE1D_MAXJ: levels per launch
+WAVE1D_MAXL = 20     # WL_WAVE1D_MAXL: taps
+
+
+def wave1d_covered(dtype, L, J=1):
+    """What the envelope of every wave-tile launcher asks of the element type, the tap count and the levels of a launch."""
+    return dtype != torch.float64 and L % 2 == 0 and L <= WAVE1D_MAXL and 1 <= J <= WAVE1D_MAXJ
+
+
+def _wave1d_covered(t, n, L, L1, J):
+    return wave1d_covered(t.dtype, L, J) and t.numel() != 0 and L1 == L and n < 1 << 30
+
+
 # ---------------------------------------------------------------------------------------------- the 1-D stationary transform
 SWT1D_FUSED = True   # up to three periodic levels per launch on the wave-tile kernels (csrc/wl_swt1d.h).  False: everything level
 #                      by level on corr1d / corr1d_adj, for A/B measurements and tests.
-SWT1D_TILE = 1024    # positions a wave holds: 64 lanes x WL_SWT1D_V of csrc/wl_swt1d.h
-SWT1D_MAXJ = 3       # WL_SWT1D_MAXJ
+SWT1D_MAXJ = WAVE1D_MAXJ
 
 
 def swt1d_core(L, J):
     """Positions of a wave's tile that are still valid after J levels of an L-tap bank: what a tile stores, and what the tiles
     of a row advance by (the seams of a row lie at multiples of it, minus `origin`)."""
-    return SWT1D_TILE - (L - 1) * (2 ** J - 1)
+    return WAVE1D_TILE - (L - 1) * (2 ** J - 1)
 
 
 def _swt1d_covered(t, L, L1, J):
-    return not (t.dtype == torch.float64 or t.numel() == 0 or J < 1 or J > SWT1D_MAXJ or L % 2 or L > 20 or L1 != L
-                or t.shape[-1] >= 1 << 30)
+    return _wave1d_covered(t, t.shape[-1], L, L1, J)
 
 
 def swt1d_fwd(x, h0, h1, nlev, origin=0, scale=1.0):
@@ -1457,8 +1471,7 @@ def wpt2d_sfb(y, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, out_hw=None, nlev=1):
 # ---------------------------------------------------------------------------------------------- the 1-D wavelet packet transform
 WPT1D_FUSED = True   # up to three periodization levels of the packet tree per launch on the wave-tile kernels (csrc/wl_wpt1d.h).
 #                      False: everything level by level on afb1d / sfb1d, for A/B measurements and tests.
-WPT1D_TILE = 1024    # positions a wave holds: 64 lanes x WL_WPT1D_V of csrc/wl_wpt1d.h
-WPT1D_MAXJ = 3       # WL_WPT1D_MAXJ
+WPT1D_MAXJ = WAVE1D_MAXJ
 
 
 def wpt1d_core(L, J):
@@ -1466,13 +1479,12 @@ def wpt1d_core(L, J):
     by (the seams of a row lie at multiples of it, minus `origin`): the tile less a halo of (L/2)(2^J - 1) positions, rounded
     up to a multiple of 2^J, on either side."""
     q = 2 ** J
-    return WPT1D_TILE - 2 * (((L // 2) * (q - 1) + q - 1) // q * q)
+    return WAVE1D_TILE - 2 * (((L // 2) * (q - 1) + q - 1) // q * q)
 
 
 def _wpt1d_covered(t, n, L, L1, mode, nlev):
     """The envelope of wl_wpt1d_analysis / wl_wpt1d_synthesis for rows of n samples (include/wavelets_hip.h)."""
-    return not (t.dtype == torch.float64 or t.numel() == 0 or nlev < 1 or nlev > WPT1D_MAXJ or mode != 2 or L % 2 or L > 20
-                or L1 != L or n >= 1 << 30 or n % 2 ** nlev or n >> (nlev - 1) < L)
+    return _wave1d_covered(t, n, L, L1, nlev) and mode == 2 and n % 2 ** nlev == 0 and n >> (nlev - 1) >= L
 
 
 def wpt1d_afb(x, h0, h1, mode, nlev, origin=0):
