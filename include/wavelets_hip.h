@@ -52,7 +52,7 @@ extern "C" {
  *          a caller that needs them looks the symbols up); wl_dtcwt1d_analysis / wl_dtcwt1d_synthesis (the 1-D DTCWT) and
  *          wl_wpt2d_analysis / wl_wpt2d_synthesis (the 2-D wavelet packet level) likewise; wl_swt1d_analysis / wl_swt1d_adjoint
  *          (the 1-D stationary transform) likewise; wl_wpt1d_analysis / wl_wpt1d_synthesis (the 1-D wavelet packet transform)
- *          likewise. */
+ *          likewise; wl_scat1d_forward / wl_scat1d_backward (the 1-D scattering layer) likewise. */
 int wl_version(void);
 const char* wl_backend(void);
 
@@ -415,6 +415,25 @@ int wl_wpt1d_analysis(const void* x, void* y, int dtype, int64_t rows, int len, 
                       int mode, int origin, void* stream);
 int wl_wpt1d_synthesis(const void* y, void* x, int dtype, int64_t rows, int len, int nlev, const void* g0, const void* g1, int L,
                        int mode, int origin, void* stream);
+
+/* One order of 1-D DTCWT scattering at one scale along the last axis (ScatLayer1D), forward and backward in ONE launch each on
+ * wave tiles (csrc/wl_scat1d.h; no LDS, no barrier).  With ne = n + (n & 1) (an odd row carries a copy of its last sample), sym
+ * the half-sample symmetric extension (a true reflection of period 2 ne: rows may be shorter than the filters) and m = L / 2,
+ *     lo[p], hi[p] = sum_j h0o[j], h1o[j] * sym(xe, p + j - m)        (the stored odd-length float taps of wl_dtcwt1d_analysis)
+ *   wl_scat1d_forward: x (batch, C, n) -> z (batch, 2C, ne/2): z[b, c, k] = (lo[2k] + lo[2k+1]) / 2 and z[b, C + c, k] = r - magbias,
+ *     r = sqrt(hi[2k]^2 + hi[2k+1]^2 + magbias^2); dir (batch, C, ne) = (hi[2k] / r, hi[2k+1] / r) interleaved, in the data
+ *     dtype, or NULL = not stored (inference: x is read once, z written once).
+ *   wl_scat1d_backward: dz (batch, 2C, ne/2) and dir -> dx (batch, C, n) by the reference's rule: dlo[s] = dz[b, c, s/2] / 2,
+ *     dhi[s] = dz[b, C + c, s/2] * dir[s], dxe = the same two correlations of sym(dlo), sym(dhi), summed; an odd n adds
+ *     dxe[n] onto dx[n-1].  magbias is ignored (dir carries it).
+ * origin: the first tile starts that many positions further left (0; tests move the tile seams with it, the results do not
+ * change by a bit), even and below the tile's core 1024 - 2 * roundup(max(L0, L1) / 2, 2).
+ * float32 / float16 / bfloat16 and (L0, L1) = (5,7), (5,3), (13,19), (9,7).  WL_ERR_UNSUPPORTED for float64, any other tap pair
+ * and rows of 2^29 samples and more: callers compose wl_dtcwt1d_analysis and element-wise operations. */
+int wl_scat1d_forward(const void* x, void* z, void* dir, int dtype, int64_t batch, int C, int n, const void* h0o, int L0,
+                      const void* h1o, int L1, double magbias, int origin, void* stream);
+int wl_scat1d_backward(const void* dz, const void* dir, void* dx, int dtype, int64_t batch, int C, int n, const void* h0o, int L0,
+                       const void* h1o, int L1, double magbias, int origin, void* stream);
 
 /* ---- single-axis building blocks -------------------------------------------------------------------------------
  * One strided / dilated correlation with boundary extension along the middle axis of a dense (outer, n, inner) tensor:

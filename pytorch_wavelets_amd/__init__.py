@@ -14,7 +14,7 @@ from .dwt.packet2d import WPT2DForward, WPT2DInverse, wpt2d_freq_order   # noqa:
 from .dwt.packet1d import WPT1DForward, WPT1DInverse, wpt1d_freq_order   # noqa: E402,F401
 from .dtcwt.transform2d import DTCWTForward, DTCWTInverse   # noqa: E402,F401
 from .dtcwt.transform1d import DTCWT1DForward, DTCWT1DInverse   # noqa: E402,F401
-from .scatternet import ScatLayer, ScatLayerj2   # noqa: E402,F401
+from .scatternet import ScatLayer, ScatLayer1D, ScatLayerj2   # noqa: E402,F401
 
 from . import parallel                                  # noqa: E402,F401
 
@@ -73,4 +73,4 @@ __all__ = ['__version__', 'last_kernel', 'launch_count', 'kernels_since', 'DTCWT
            'DWT', 'IDWT', 'DWT2D', 'IDWT2D', 'DWT1DForward', 'DWT1DInverse', 'DWT1D', 'IDWT1D', 'ScatLayer', 'ScatLayerj2',
            'DWT3DForward', 'DWT3DInverse', 'DWT3D', 'IDWT3D', 'DTCWT1DForward', 'DTCWT1DInverse', 'DTCWT1D', 'IDTCWT1D',
            'WPT2DForward', 'WPT2DInverse', 'WPT2D', 'IWPT2D', 'wpt2d_freq_order', 'SWT1DForward', 'SWT1DInverse', 'SWT1D',
-           'ISWT1D', 'WPT1DForward', 'WPT1DInverse', 'WPT1D', 'IWPT1D', 'wpt1d_freq_order']
+           'ISWT1D', 'WPT1DForward', 'WPT1DInverse', 'WPT1D', 'IWPT1D', 'wpt1d_freq_order', 'ScatLayer1D']

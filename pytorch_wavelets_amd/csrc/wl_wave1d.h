@@ -1,10 +1,10 @@
-// Wave tiles: what the barrier-free 1-D kernels along the last axis (wl_swt1d.h, wl_wpt1d.h) share.  No LDS, no workgroup
-// barrier, no role split.
+// Wave tiles: what the barrier-free 1-D kernels along the last axis (wl_swt1d.h, wl_wpt1d.h, wl_scat1d.h) share.  No LDS, no
+// workgroup barrier, no role split.
 //
 //   * a WAVE owns a tile of 64 * V consecutive UNFOLDED positions of one row: position p is sample p mod len (a true floor-mod:
 //     tiles start left of 0, and a row may be shorter than the filter and wrap many times inside one tile).  The transforms here
 //     are periodic with the row's period at every level, so the cascade runs on the unfolded coordinates and no level has
-//     boundary logic;
+//     boundary logic (the scattering layer: the symmetric extension of a row is periodic, wl_wave1d_load_sym);
 //   * lane l holds positions a + l*V .. a + l*V + V - 1 in registers, as float.  A source at compile-time offset M from a run of
 //     VJ registers of the lane lives in register M mod VJ of lane l + floor(M / VJ): the lane's own register when the quotient
 //     is 0, one wl_shfl otherwise (wl_wave1d_fetch).  The sources of a level are walked in ascending position, each fetched
@@ -64,6 +64,47 @@ WL_DEV void wl_wave1d_load(const T* run, int s0, int len, float (&r)[V], int off
             for (int e = 0; e < E; ++e) {
                 r[off + k + e] = (float)run[s];
                 s = s + 1 == len ? 0 : s + 1;
+            }
+        }
+    }
+}
+
+// The half-sample symmetric fold of a row of n elements that stands for ne = n + (n & 1) samples (an odd row carries a copy of
+// its last sample behind it): q, a position already reduced to the period [0, 2 ne), is element
+//     s = q < ne ? q : 2 ne - 1 - q,    s == n -> n - 1.
+// A true reflection of period 2 ne: a row may be shorter than the filter and fold many times inside one tile.
+WL_DEV int wl_wave1d_fold(int q, int n, int ne) {
+    const int s = q < ne ? q : 2 * ne - 1 - q;
+    return s < n ? s : n - 1;
+}
+
+// The symmetric counterpart of wl_wave1d_load: N consecutive unfolded positions from p0 on (any sign) of a row of n elements
+// under that fold, into r[off .. off + N).  A piece whose positions map ascending into [0, n) is one access, any other piece
+// goes element by element.  Only the pieces that meet the window [w0, w1) are loaded (what the stored core needs of the tile:
+// a row's last tile, or a short row's only one, lies mostly outside it); the others are zeros that no stored output reads.
+template <typename T, int N, int V>
+WL_DEV void wl_wave1d_load_sym(const T* run, int p0, int n, int ne, int w0, int w1, float (&r)[V], int off) {
+    constexpr int E = WlWaveRun<T, N>::E;
+    static_assert(N % E == 0, "a lane holds whole pieces");
+    const int q0 = wl_pmod(p0, 2 * ne);
+#pragma unroll
+    for (int k = 0; k < N; k += E) {
+        if (p0 + k + E <= w0 || p0 + k >= w1) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) r[off + k + e] = 0.f;
+            continue;
+        }
+        int q = q0 + k;
+        if (q >= 2 * ne) q %= 2 * ne;
+        if (q + E <= n) {
+            const typename WlWavePiece<T, E>::type v = *reinterpret_cast<const typename WlWavePiece<T, E>::type*>(run + q);
+#pragma unroll
+            for (int e = 0; e < E; ++e) r[off + k + e] = (float)v[e];
+        } else {
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                r[off + k + e] = (float)run[wl_wave1d_fold(q, n, ne)];
+                q = q + 1 == 2 * ne ? 0 : q + 1;
             }
         }
     }

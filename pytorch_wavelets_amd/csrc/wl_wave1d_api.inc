@@ -1,9 +1,10 @@
-// C ABI of the wave-tile kernels (wl_wave1d.h): the 1-D stationary transform (wl_swt1d.h) and the 1-D wavelet packet transform
-// (wl_wpt1d.h).  Included at the end of wl_dtcwt1d_api.inc, so compiled in the fourth translation unit of the HIP build
+// C ABI of the wave-tile kernels (wl_wave1d.h): the 1-D stationary transform (wl_swt1d.h), the 1-D wavelet packet transform
+// (wl_wpt1d.h) and the 1-D scattering layer (wl_scat1d.h).  Included at the end of wl_dtcwt1d_api.inc, so compiled in the fourth translation unit of the HIP build
 // (wl_dtinv_hip.hip) and in the matching unit of the host emulation.
 #include "wl_api_common.h"
 #include "wl_swt1d.h"
 #include "wl_wpt1d.h"
+#include "wl_scat1d.h"
 
 // the grid of a launch: tiles of `core` positions from -origin on, WL_WAVE1D_WAVES tiles per workgroup
 struct WlWave1dGrid { int core, tiles; int64_t waves, nblocks; };
@@ -128,3 +129,67 @@ extern "C" int wl_wpt1d_synthesis(const void* y, void* x, int dtype, int64_t row
     WL_WPT1D_ENTRY(WlWpt1dSfb, y, x, g0, g1);
 }
 #undef WL_WPT1D_ENTRY
+
+// ---- the 1-D scattering layer: two odd tap counts, one level, the symmetric fold.  Its own checks (wl_wave1d_check insists on
+// one even L), the same order of the codes.
+static bool wl_scat1d_pair(int L0, int L1) {
+    return (L0 == 5 && L1 == 7) || (L0 == 5 && L1 == 3) || (L0 == 13 && L1 == 19) || (L0 == 9 && L1 == 7);
+}
+
+static int wl_scat1d_grid(int64_t batch, int C, int n, int L0, int L1, int dtype, int origin, WlWave1dGrid& g) {
+    if (batch < 0 || C < 0 || n < 1 || L0 < 1 || L1 < 1 || origin < 0) return WL_ERR_SHAPE;
+    if (dtype != WL_F32 && dtype != WL_F16 && dtype != WL_BF16) return dtype == WL_F64 ? WL_ERR_UNSUPPORTED : WL_ERR_DTYPE;
+    if (!wl_scat1d_pair(L0, L1) || n >= (1 << 29)) return WL_ERR_UNSUPPORTED;      // (the fold's period 2 ne is an int)
+    if (origin & 1) return WL_ERR_SHAPE;                                           // a lane holds whole (2k, 2k+1) pairs
+    const int M = (L0 > L1 ? L0 : L1) / 2, head = (M + 1) / 2 * 2;
+    return wl_wave1d_grid(batch * C, n + (n & 1), origin, 64 * WL_WAVE1D_V - 2 * head, g);
+}
+
+#define WL_SCAT1D_BY_TAPS(K, a, g, stream)                                                     \
+    switch (L0 * 100 + L1) {                                                                   \
+        case 507: return wl_launch<K<T, 5, 7> >(a, g.nblocks, 0, stream);                      \
+        case 503: return wl_launch<K<T, 5, 3> >(a, g.nblocks, 0, stream);                      \
+        case 1319: return wl_launch<K<T, 13, 19> >(a, g.nblocks, 0, stream);                   \
+        default: return wl_launch<K<T, 9, 7> >(a, g.nblocks, 0, stream);                       \
+    }
+
+#define WL_SCAT1D_FILL(a, g)                                                                   \
+    a.h0 = (const float*)h0o; a.h1 = (const float*)h1o;                                        \
+    a.rows = batch * C; a.waves = g.waves; a.C = C; a.n = n; a.len = n + (n & 1);              \
+    a.tiles = g.tiles; a.core = g.core; a.origin = origin
+
+extern "C" int wl_scat1d_forward(const void* x, void* z, void* dir, int dtype, int64_t batch, int C, int n, const void* h0o, int L0,
+                                 const void* h1o, int L1, double magbias, int origin, void* stream) {
+    WlWave1dGrid g;
+    const int rc = wl_scat1d_grid(batch, C, n, L0, L1, dtype, origin, g);
+    if (rc != 0) return rc;
+    if (!x || !z) return WL_ERR_SHAPE;
+    if (!h0o || !h1o) return WL_ERR_TAPS;
+    if (batch * C == 0) return 0;
+    WL_DISPATCH_FLOAT(dtype, {
+        WlScat1dFwdArgs<T> a;
+        a.x = (const T*)x; a.z = (T*)z; a.dir = (T*)dir;
+        WL_SCAT1D_FILL(a, g);
+        a.bias = (float)magbias;
+        WL_SCAT1D_BY_TAPS(WlScat1dFwd, a, g, stream)
+    });
+}
+
+extern "C" int wl_scat1d_backward(const void* dz, const void* dir, void* dx, int dtype, int64_t batch, int C, int n, const void* h0o,
+                                  int L0, const void* h1o, int L1, double magbias, int origin, void* stream) {
+    (void)magbias;                                      // (the directions carry it)
+    WlWave1dGrid g;
+    const int rc = wl_scat1d_grid(batch, C, n, L0, L1, dtype, origin, g);
+    if (rc != 0) return rc;
+    if (!dz || !dir || !dx) return WL_ERR_SHAPE;
+    if (!h0o || !h1o) return WL_ERR_TAPS;
+    if (batch * C == 0) return 0;
+    WL_DISPATCH_FLOAT(dtype, {
+        WlScat1dBwdArgs<T> a;
+        a.dz = (const T*)dz; a.dir = (const T*)dir; a.dx = (T*)dx;
+        WL_SCAT1D_FILL(a, g);
+        WL_SCAT1D_BY_TAPS(WlScat1dBwd, a, g, stream)
+    });
+}
+#undef WL_SCAT1D_FILL
+#undef WL_SCAT1D_BY_TAPS

@@ -1400,8 +1400,76 @@ def swt1d_adj(lo, his, g0, g1, scale, origin=0):
     return y
 
 
+# ---------------------------------------------------------------------------------------------- the 1-D scattering layer
+SCAT1D_FUSED = True   # ScatLayer1D forward and backward in one launch each on the wave-tile kernels (csrc/wl_scat1d.h).  False:
+#                       level 1 of the 1-D DTCWT plus element-wise torch operations and autograd, for A/B measurements and tests.
+SCAT1D_PAIRS = ((5, 7), (5, 3), (13, 19), (9, 7))   # (L0, L1) the kernels are instantiated for: near_sym_a, legall, near_sym_b, antonini
+SCAT1D_MIN_LEN = 0    # rows shorter than this take the composition.  One wave serves one row, but the fused route still wins 3.7x
+#                       at rows of 64 samples, the shortest measured: none do.
+
+
+def scat1d_core(L0, L1):
+    """Positions of a wave's tile the scattering kernels store, and what the tiles of a row advance by: the tile less the halo
+    of the longer filter, rounded up to even, on either side."""
+    return WAVE1D_TILE - 2 * ((max(L0, L1) // 2 + 1) // 2 * 2)
+
+
+def scat1d_covered(x, h0o, h1o):
+    """What the fused route asks: the switch, the element type, an instantiated tap pair, a row the policy sends there."""
+    return (SCAT1D_FUSED and x.dtype != torch.float64 and (h0o.numel(), h1o.numel()) in SCAT1D_PAIRS and x.numel() != 0
+            and SCAT1D_MIN_LEN <= x.shape[-1] < 1 << 29)
+
+
+def scat1d_fwd(x, h0o, h1o, magbias, save, origin=0):
+    """ScatLayer1D in ONE launch (wl_scat1d_forward): x (N, C, n) -> (Z (N, 2C, ceil(n/2)), dir): Z = [pair means of the lowpass
+    x C, smoothed magnitudes of the highpass pairs x C]; dir (N, C, n + n % 2) = the pairs over their root, what the backward
+    needs, or None without `save`.  None when the launcher declines (float64, other tap counts): callers compose the 1-D DTCWT.
+    `origin` (tests) moves the tile seams."""
+    _check_tensor(x, 'x')
+    L0, L1 = h0o.numel(), h1o.numel()
+    if x.ndim != 3 or x.dtype == torch.float64 or (L0, L1) not in SCAT1D_PAIRS or x.numel() == 0 or x.shape[-1] >= 1 << 29:
+        return None
+    N, C, n = x.shape
+    key = ('scat1d_fwd', x.device, x.dtype, N, C, n, L0, L1)
+    if key in _FUSED_DECLINED:
+        return None
+    x = x.contiguous()
+    t0, t1 = _taps(h0o, x), _taps(h1o, x)
+    ne = n + n % 2
+    z = torch.empty((N, 2 * C, ne // 2), dtype=x.dtype, device=x.device)
+    d = torch.empty((N, C, ne), dtype=x.dtype, device=x.device) if save else None
+    if _declined(key, 'wl_scat1d_forward', x, x.data_ptr(), z.data_ptr(), d.data_ptr() if save else None, _DTYPES[x.dtype], N, C, n,
+                 t0.data_ptr(), L0, t1.data_ptr(), L1, float(magbias), int(origin), _stream(x)):
+        return None
+    return z, d
+
+
+def scat1d_bwd(dz, d, h0o, h1o, n, origin=0):
+    """The backward of scat1d_fwd in ONE launch (wl_scat1d_backward): dz (N, 2C, ceil(n/2)) and the saved dir -> dx (N, C, n) by
+    the reference's rule (ScatLayerj1_f.backward on one axis).  None when the launcher declines."""
+    _check_tensor(dz, 'dz')
+    _same_device(dz, d)
+    L0, L1 = h0o.numel(), h1o.numel()
+    N, C, ne = d.shape
+    if dz.dtype != d.dtype or tuple(dz.shape) != (N, 2 * C, ne // 2) or ne != n + n % 2:
+        raise ValueError('scat1d_bwd: dz %s %s does not belong to dir %s %s of rows of %d samples'
+                         % (tuple(dz.shape), dz.dtype, tuple(d.shape), d.dtype, n))
+    if dz.dtype == torch.float64 or (L0, L1) not in SCAT1D_PAIRS or dz.numel() == 0 or n >= 1 << 29:
+        return None
+    key = ('scat1d_bwd', dz.device, dz.dtype, N, C, n, L0, L1)
+    if key in _FUSED_DECLINED:
+        return None
+    dz, d = dz.contiguous(), d.contiguous()
+    t0, t1 = _taps(h0o, dz), _taps(h1o, dz)
+    dx = torch.empty((N, C, n), dtype=dz.dtype, device=dz.device)
+    if _declined(key, 'wl_scat1d_backward', dz, dz.data_ptr(), d.data_ptr(), dx.data_ptr(), _DTYPES[dz.dtype], N, C, n,
+                 t0.data_ptr(), L0, t1.data_ptr(), L1, 0.0, int(origin), _stream(dz)):
+        return None
+    return dx
+
+
 # ---------------------------------------------------------------------------------------------- the 2-D wavelet packet level
-WPT_FUSED = True   # two packet levels per launch where the kernels take them (periodization, sizes multiples of 4, <= 12 taps):
+WPT_FUSED = True  # two packet levels per launch where the kernels take them (periodization, sizes multiples of 4, <= 12 taps):
 #                    measured ahead of one launch per level (DESIGN.md 4.27).  False: everything level by level, for A/B measurements.
 
 

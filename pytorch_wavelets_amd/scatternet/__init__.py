@@ -1,1 +1,1 @@
-from .layers import ScatLayer, ScatLayerj2   # noqa: F401
+from .layers import ScatLayer, ScatLayer1D, ScatLayerj2   # noqa: F401

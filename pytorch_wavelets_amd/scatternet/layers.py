@@ -1,10 +1,10 @@
-"""ScatLayer (reference pytorch_wavelets/scatternet/layers.py:11-79)."""
+"""ScatLayer, ScatLayerj2 (reference pytorch_wavelets/scatternet/layers.py:11-172) and ScatLayer1D, ScatLayer on one axis."""
 import torch
 import torch.nn as nn
 
 from ..dtcwt.lowlevel import prep_filt
 from ..filters import biort as _biort, qshift as _qshift
-from .lowlevel import ScatLayerj1_f, mode_to_int, scat_layer_j1_rot, scat_layer_j2, scat_layer_j2_rot
+from .lowlevel import ScatLayerj1_f, mode_to_int, scat_layer1d, scat_layer_j1_rot, scat_layer_j2, scat_layer_j2_rot
 
 
 class ScatLayer(nn.Module):
@@ -112,6 +112,35 @@ class ScatLayerj2(nn.Module):
             b, _, c, h, w = Z.shape
             Z = Z.reshape(b, 49 * c, h, w)
         return Z
+
+    def extra_repr(self):
+        return "biort='{}', mode='{}', magbias={}".format(self.biort, self.mode_str, self.magbias)
+
+
+class ScatLayer1D(nn.Module):
+    """One order of DTCWT scattering at one scale on signals: ``ScatLayer1D(biort='near_sym_a', mode='symmetric',
+    magbias=1e-2)(x: (N, C, n)) -> (N, 2C, ceil(n/2))`` with channel order [lowpass x C, magnitude x C] - ScatLayer on one
+    axis.  Level 1 of DTCWT1DForward (an odd n gets a copy of its last sample), then per pair of samples the mean of the lowpass
+    and ``sqrt(re^2 + im^2 + magbias^2) - magbias`` of the analytic band.  Two layers in a row give second order.  `biort` is a
+    name or an (h0o, h1o) pair; the four named pairs of 5/7, 5/3, 13/19 and 9/7 taps run as one launch per direction."""
+
+    def __init__(self, biort='near_sym_a', mode='symmetric', magbias=1e-2):
+        super().__init__()
+        if mode != 'symmetric':
+            raise ValueError("ScatLayer1D implements mode 'symmetric' only, got {!r}".format(mode))
+        self.biort = biort
+        self.mode_str = mode
+        self.magbias = magbias
+        if isinstance(biort, str):
+            h0o, _, h1o, _ = _biort(biort)[:4]
+        else:
+            h0o, h1o = biort[0], biort[1]
+        self.h0o = torch.nn.Parameter(prep_filt(h0o, 1), False)
+        self.h1o = torch.nn.Parameter(prep_filt(h1o, 1), False)
+
+    def forward(self, x):
+        assert x.ndim == 3, "Can only handle 3d inputs (N, C, L)"
+        return scat_layer1d(x, self.h0o, self.h1o, self.magbias)
 
     def extra_repr(self):
         return "biort='{}', mode='{}', magbias={}".format(self.biort, self.mode_str, self.magbias)

@@ -301,3 +301,50 @@ def scat_layer_j2_rot(x, h0o, h1o, h2o, h0a, h0b, h1a, h1b, h2a, h2b, mode, bias
     if combine_colour:
         return torch.cat((s0, s1p, s1_j2[:, :, 0], s2_j1.reshape(n, 36, h, w)), dim=1)
     return torch.cat((s0[:, None], s1p.reshape(n, 6, c, h, w), s1_j2, s2_j1.reshape(n, 36, c, h, w)), dim=1)
+
+
+class ScatLayer1D_f(Function):
+    """ScatLayer1D on the wave-tile kernels (csrc/wl_scat1d.h): ``apply(x, h0o, h1o, bias, save) -> Z``; the forward is one
+    launch, which also stores the directions (hi[2k] / r, hi[2k+1] / r) when `save` asks for them - the caller's
+    ``torch.is_grad_enabled() and x.requires_grad``: inside a Function the grad mode is always off -, the backward one launch
+    fed with them (the rule of ScatLayerj1_f.backward on one axis)."""
+
+    @staticmethod
+    def forward(ctx, x, h0o, h1o, bias, save):
+        res = ops.scat1d_fwd(x, h0o, h1o, bias, save)
+        if res is None:
+            raise NotImplementedError('ScatLayer1D: no wave-tile kernel for %s data and %d / %d taps'
+                                      % (x.dtype, h0o.numel(), h1o.numel()))
+        Z, d = res
+        ctx.n = x.shape[-1]
+        if save:
+            ctx.save_for_backward(h0o, h1o, d)
+        return Z
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dZ):
+        dX = None
+        if ctx.needs_input_grad[0]:
+            h0o, h1o, d = ctx.saved_tensors
+            dX = ops.scat1d_bwd(dZ, d, h0o, h1o, ctx.n)
+            if dX is None:
+                raise NotImplementedError('ScatLayer1D: no wave-tile kernel for the backward of %s data' % dZ.dtype)
+        return (dX,) + (None,) * 4
+
+
+def scat_layer1d(x, h0o, h1o, bias):
+    """ScatLayer1D of x (N, C, n) -> (N, 2C, ceil(n/2)): the fused kernels where they cover the configuration
+    (ops.scat1d_covered), else the composition - level 1 of the 1-D DTCWT node (an odd row gets a copy of its last sample
+    there), element-wise torch operations and autograd."""
+    ops._check_tensor(x, 'x')
+    if x.numel() == 0:
+        Z = x.new_zeros((x.shape[0], 2 * x.shape[1], (x.shape[2] + 1) // 2))
+        return Z + 0 * x.sum() if x.requires_grad else Z
+    if ops.scat1d_covered(x, h0o, h1o):
+        return ScatLayer1D_f.apply(x, h0o, h1o, bias, torch.is_grad_enabled() and x.requires_grad)
+    from ..dtcwt.transform_funcs import DTCWT1DAnalysis
+    # (one level: the q-shift slots of the node are never read)
+    lo, hi = DTCWT1DAnalysis.apply(x, h0o, h1o, h0o, h0o, h1o, h1o, False, (False,), (False,))[:2]
+    mag = torch.sqrt(hi[..., 0::2] ** 2 + hi[..., 1::2] ** 2 + bias * bias) - bias
+    return torch.cat((0.5 * (lo[..., 0::2] + lo[..., 1::2]), mag), 1)
