@@ -433,8 +433,9 @@ def _npy(t):
     return t.detach().cpu().double().numpy()
 
 
-def check(case, dev, seed=11):
-    """Checks (a) - (e) of the module docstring; returns [(output index, max error, bound)]."""
+def check(case, dev, seed=11, outs_to=None):
+    """Checks (a) - (e) of the module docstring; returns [(output index, max error, bound)].  `outs_to`: a list that receives
+    the output tensors of the view call (tests/_guard_cases.py looks at where they lie)."""
     backend = _backend_of(dev)
     host = _inputs(case, dev, seed)
     ops._FUSED_DECLINED.clear()
@@ -461,6 +462,8 @@ def check(case, dev, seed=11):
     # (a), (b)
     refs = oracle(*[_npy(t) for t in host])
     assert len(refs) == len(outs), (len(refs), len(outs))
+    if outs_to is not None:
+        outs_to.extend(outs)
     errs = []
     for i, (o, ref) in enumerate(zip(outs, refs)):
         assert o.dtype == case.dtype and tuple(o.shape) == ref.shape, (i, o.dtype, tuple(o.shape), ref.shape)
@@ -477,10 +480,10 @@ def check(case, dev, seed=11):
     return errs
 
 
-def check_grad(case, dev, seed=12):
+def check_grad(case, dev, seed=12, outs_to=None):
     """torch.autograd.grad through the case's transform: every input a crop view (the case's own makers where it has several
     inputs), every gradient output an offset(1) view; against the gradients of dense aligned clones on the per-level tile
-    path, which must be full tensors without NaN."""
+    path, which must be full tensors without NaN.  `outs_to`: a list that receives the gradients of the view call."""
     host = _inputs(case, dev, seed)
     rng = np.random.RandomState(seed + 1)
     ops._FUSED_DECLINED.clear()
@@ -508,6 +511,8 @@ def check_grad(case, dev, seed=12):
     _sync(dev)
     print('%s %s backward: view %s, reference %s' % (case.name, case.tf.name, k_view, k_ref))
     assert not any('Strip' in k or 'Rows' in k for k in k_ref), k_ref
+    if outs_to is not None:
+        outs_to.extend(grads)
     errs = []
     for i, (g, r, x) in enumerate(zip(grads, ref, xs)):
         assert g.shape == x.shape and g.dtype == case.dtype
