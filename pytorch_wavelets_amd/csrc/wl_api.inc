@@ -809,6 +809,10 @@ extern "C" int wl_corr1d(const void* x, void* y0, void* y1, int dtype, int64_t o
     if (ext < 0 || ext > WL_EXT_PER_FOLD1) return WL_ERR_MODE;
     if (ext == WL_EXT_PER_FOLD1 && (step != 2 || tap_step != 1 || start != 1 - ntaps)) return WL_ERR_SHAPE;
     if (outer == 0 || K == 0) return 0;
+    {   // the kernel holds extended positions in an int: the last one a thread forms must be one (a row within a filter length of 2^31)
+        const int64_t last = (int64_t)start + (int64_t)step * (K - 1) + (int64_t)tap_step * (ntaps - 1) + (ext == WL_EXT_PER_FOLD1 ? (int64_t)n + 1 : 0);
+        if (last > 2147483647LL) return WL_ERR_UNSUPPORTED;
+    }
     WL_DISPATCH_DTYPE(dtype, {
         typedef typename WlAcc<T>::type A;
         WlCorr1dArgs<T> a;
@@ -1150,6 +1154,8 @@ extern "C" int wl_corr1d_adj(const void* y0, int64_t y0_outer_stride, const void
     if (outer < 0 || n < 1 || inner < 1 || K < 0 || ntaps < 1 || ntaps > WL_MAX_TAPS || tap_step < 1 || !y0) return WL_ERR_SHAPE;
     if (y1 && !h1) return WL_ERR_SHAPE;
     if (ext < 0 || ext > WL_EXT_REPLICATE || ext == WL_EXT_PER) return WL_ERR_MODE;
+    // the kernel walks extended positions up to 2n + the pad in an int
+    if (n >= (1 << 30)) return WL_ERR_UNSUPPORTED;
     if (outer == 0) return 0;
     WL_DISPATCH_DTYPE(dtype, {
         typedef typename WlAcc<T>::type A;

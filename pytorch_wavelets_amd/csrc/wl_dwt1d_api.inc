@@ -82,7 +82,7 @@ extern "C" int wl_dwt1d_analysis_fused(const void* x, void* lo, void* const* hig
     if (J > WL_DWT1D_MAXJ || !highs || !lo || !x) return WL_ERR_UNSUPPORTED;
     if (rows == 0) return 0;
     if (mode == 2 && N + (N & 1) < L - 1) return WL_ERR_UNSUPPORTED;       // single-fold corner of the reference: wl_corr1d's literal form
-    if ((int64_t)rows * N >= (1LL << 40)) return WL_ERR_UNSUPPORTED;
+    if ((int64_t)rows * N >= (1LL << 40) || N >= (1 << 30)) return WL_ERR_UNSUPPORTED;   // (wl_ext folds with the period 2N: an int)
     int n[WL_DWT1D_MAXJ + 1], base[WL_DWT1D_MAXJ];
     n[0] = N;
     for (int j = 0; j < J; ++j) {

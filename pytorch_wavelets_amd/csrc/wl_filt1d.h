@@ -22,6 +22,15 @@
 
 WL_HD int wl_ext_any(int i, int n, int ext) {
     if (ext == WL_EXT_REPLICATE) return i < 0 ? 0 : (i >= n ? n - 1 : i);
+    if (n >= (1 << 30) && (unsigned)i >= (unsigned)n && (ext == WL_EXT_SYM || ext == WL_EXT_REFL)) {
+        // the period of the fold, 2n (2n - 2), is no int: wl_ext would wrap it.  No launcher bounds the length of a single axis
+        // (the level-by-level route of every 1-D analysis above 2^30 samples ends here; wl_corr1d bounds the positions it hands in)
+        const int s = ext == WL_EXT_SYM ? 1 : 0;
+        const int64_t p = 2 * (int64_t)n - 2 + 2 * s;
+        int64_t j = i % p;
+        if (j < 0) j += p;
+        return (int)(j < n ? j : p - s - j);
+    }
     return wl_ext(i, n, ext);
 }
 

@@ -10,6 +10,12 @@ from .. import ops
 from ..dwt.lowlevel import int_to_mode, mode_to_int   # noqa: F401  (re-exported like upstream)
 
 
+def _up2(t):
+    """Every sample of the last two axes twice (nearest-neighbour upsampling by 2).  F.interpolate refuses planes of more than 65535
+    rows ("spatial dimension larger than the kernel capacity"): the backward pass of a plane above the fused kernel's limit ended there."""
+    return t.repeat_interleave(2, dim=-2).repeat_interleave(2, dim=-1)
+
+
 class ScatLayerj1_f(Function):
     @staticmethod
     def forward(ctx, x, h0o, h1o, mode, bias, combine_colour):
@@ -38,7 +44,7 @@ class ScatLayerj1_f(Function):
                     dr = dr[:, :, None]
                 else:
                     dYl, dr = dZ[:, 0], dZ[:, 1:]
-                ll = 0.25 * F.interpolate(dYl, scale_factor=2, mode="nearest")
+                ll = 0.25 * _up2(dYl)
                 # (N,6,C,h,w) real / imag -> default coefficient layout (N,C,6,h,w,2)
                 highs = torch.stack((dr * drdx, dr * drdy), dim=-1).permute(0, 2, 1, 3, 4, 5).contiguous()
                 dX = ops.dtcwt_inv1(ll, highs, h0o, h1o, ctx.mode)
@@ -82,7 +88,7 @@ class ScatLayerj1_ll_f(Function):
                     dr = dr[:, :, None]
                 else:
                     dYl, dr = dZ[:, 0], dZ[:, 1:]
-                ll = 0.25 * F.interpolate(dYl, scale_factor=2, mode="nearest")
+                ll = 0.25 * _up2(dYl)
                 highs = torch.stack((dr * drdx, dr * drdy), dim=-1).permute(0, 2, 1, 3, 4, 5).contiguous()
                 dX = ops.dtcwt_inv1(ll + dll, highs, h0o, h1o, ctx.mode)
             else:
@@ -162,7 +168,7 @@ def _scat_bwd1_any(dZ, drdx, drdy, h0o, h1o, mode, combine_colour=False):
             dr = dr[:, :, None]
         else:
             dYl, dr = dZ[:, 0], dZ[:, 1:]
-        ll = 0.25 * F.interpolate(dYl, scale_factor=2, mode="nearest")
+        ll = 0.25 * _up2(dYl)
         highs = torch.stack((dr * drdx, dr * drdy), dim=-1).permute(0, 2, 1, 3, 4, 5).contiguous()
         dX = ops.dtcwt_inv1(ll, highs, h0o, h1o, mode)
     return dX

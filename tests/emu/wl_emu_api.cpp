@@ -11,3 +11,5 @@ extern "C" void wl_emu_set_schedule(int order, int dma, unsigned seed) {
     wl_emu_dma_v = dma == 1 ? 1 : 0;
     wl_emu_seed_v = seed;
 }
+// test hook (emulator only): the extension rule of the single-axis kernels (wl_filt1d.h), for lengths no test can allocate on the host
+extern "C" int wl_emu_ext_any(int i, int n, int ext) { return wl_ext_any(i, n, ext); }

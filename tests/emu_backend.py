@@ -72,3 +72,11 @@ def ring_slot_fn():
     f = ctypes.CDLL(_SO).wl_emu_ring_slot
     f.argtypes, f.restype = [ctypes.c_int, ctypes.c_int], ctypes.c_int
     return f
+
+
+def ext_any_fn():
+    """ext(i, n, rule): the source position of extended position i of an n-sample axis, as the single-axis kernels compute it."""
+    handle()
+    f = ctypes.CDLL(_SO).wl_emu_ext_any
+    f.argtypes, f.restype = [ctypes.c_int, ctypes.c_int, ctypes.c_int], ctypes.c_int
+    return f
