@@ -52,7 +52,8 @@ extern "C" {
  *          a caller that needs them looks the symbols up); wl_dtcwt1d_analysis / wl_dtcwt1d_synthesis (the 1-D DTCWT) and
  *          wl_wpt2d_analysis / wl_wpt2d_synthesis (the 2-D wavelet packet level) likewise; wl_swt1d_analysis / wl_swt1d_adjoint
  *          (the 1-D stationary transform) likewise; wl_wpt1d_analysis / wl_wpt1d_synthesis (the 1-D wavelet packet transform)
- *          likewise; wl_scat1d_forward / wl_scat1d_backward (the 1-D scattering layer) likewise. */
+ *          likewise; wl_scat1d_forward / wl_scat1d_backward (the 1-D scattering layer) likewise; wl_shrink1d_forward /
+ *          wl_shrink1d_backward (shrinkage of the 1-D stationary transform) likewise. */
 int wl_version(void);
 const char* wl_backend(void);
 
@@ -434,6 +435,29 @@ int wl_scat1d_forward(const void* x, void* z, void* dir, int dtype, int64_t batc
                       const void* h1o, int L1, double magbias, int origin, void* stream);
 int wl_scat1d_backward(const void* dz, const void* dir, void* dx, int dtype, int64_t batch, int C, int n, const void* h0o, int L0,
                        const void* h1o, int L1, double magbias, int origin, void* stream);
+
+/* Wavelet shrinkage of the 1-D stationary transform along the last axis (SWT1DShrink), forward and backward in ONE launch each on
+ * wave tiles (csrc/wl_shrink1d.h; no LDS, no barrier, no atomics): x (rows, n) -> y (rows, n),
+ *     lo_J, hi_1 .. hi_J = J levels of wl_swt1d_analysis (periodic, stored taps h0 / h1, scale 1),
+ *     hi_j' = sign(hi_j) max(|hi_j| - t, 0) (kind 0, soft) or hi_j [|hi_j| > t] (kind 1, hard), t = thr[j * rows + row],
+ *     y = wl_swt1d_adjoint of (lo_J, hi') with the taps g0 / g1 and 1/2 per level.
+ * thr is float32 whatever the data type and is used as given (no clamp).  The coefficients never leave registers: x is read
+ * once and y written once whatever J.
+ *   wl_shrink1d_backward: x, dy -> dx; it recomputes the coefficients (the forward's bits) and keeps [|hi_j| > t] and the sign of
+ *     each.  dhi_j = the analysis of dy with g0 / g1 and 1/2 per level; dx = the transposed cascade of (dlo, dhi_j [|hi_j| > t])
+ *     with h0 / h1.  dthr_part (float32, rows x tiles x J with tiles = ceil((n + origin) / core)), or NULL = not wanted:
+ *     dthr_part[(row * tiles + tile) * J + j] = - sum over the tile's core of sign(hi_j) [|hi_j| > t] dhi_j for kind 0, zeros for
+ *     kind 1; the caller sums over tiles.
+ * origin: the first tile starts that many positions further left (0; tests move the tile seams with it), below the tile's core
+ * 1024 - 2 (L - 1)(2^J - 1).
+ * float32 / float16 / bfloat16, even L <= 20, J = 1..3, kind 0 or 1.  WL_ERR_UNSUPPORTED outside that envelope (float64, odd L,
+ * L > 20, J > 3, another kind): callers compose wl_swt1d_analysis, element-wise operations and wl_swt1d_adjoint.  J < 1 is
+ * WL_ERR_SHAPE, as in the other wave-tile entries. */
+int wl_shrink1d_forward(const void* x, void* y, const void* thr, int dtype, int64_t rows, int n, int J, const void* h0,
+                        const void* h1, const void* g0, const void* g1, int L, int kind, int origin, void* stream);
+int wl_shrink1d_backward(const void* x, const void* dy, void* dx, const void* thr, void* dthr_part, int dtype, int64_t rows, int n,
+                         int J, const void* h0, const void* h1, const void* g0, const void* g1, int L, int kind, int origin,
+                         void* stream);
 
 /* ---- single-axis building blocks -------------------------------------------------------------------------------
  * One strided / dilated correlation with boundary extension along the middle axis of a dense (outer, n, inner) tensor:

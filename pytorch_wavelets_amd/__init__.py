@@ -9,6 +9,7 @@ __version__ = '0.1.0'
 from .dwt.transform2d import DWTForward, DWTInverse   # noqa: E402,F401
 from .dwt.transform1d import DWT1DForward, DWT1DInverse   # noqa: E402,F401
 from .dwt.swt1d import SWT1DForward, SWT1DInverse   # noqa: E402,F401
+from .dwt.shrink1d import SWT1DShrink, swt1d_universal_thresh   # noqa: E402,F401
 from .dwt.transform3d import DWT3DForward, DWT3DInverse   # noqa: E402,F401
 from .dwt.packet2d import WPT2DForward, WPT2DInverse, wpt2d_freq_order   # noqa: E402,F401
 from .dwt.packet1d import WPT1DForward, WPT1DInverse, wpt1d_freq_order   # noqa: E402,F401
@@ -73,4 +74,5 @@ __all__ = ['__version__', 'last_kernel', 'launch_count', 'kernels_since', 'DTCWT
            'DWT', 'IDWT', 'DWT2D', 'IDWT2D', 'DWT1DForward', 'DWT1DInverse', 'DWT1D', 'IDWT1D', 'ScatLayer', 'ScatLayerj2',
            'DWT3DForward', 'DWT3DInverse', 'DWT3D', 'IDWT3D', 'DTCWT1DForward', 'DTCWT1DInverse', 'DTCWT1D', 'IDTCWT1D',
            'WPT2DForward', 'WPT2DInverse', 'WPT2D', 'IWPT2D', 'wpt2d_freq_order', 'SWT1DForward', 'SWT1DInverse', 'SWT1D',
-           'ISWT1D', 'WPT1DForward', 'WPT1DInverse', 'WPT1D', 'IWPT1D', 'wpt1d_freq_order', 'ScatLayer1D']
+           'ISWT1D', 'WPT1DForward', 'WPT1DInverse', 'WPT1D', 'IWPT1D', 'wpt1d_freq_order', 'ScatLayer1D',
+           'SWT1DShrink', 'swt1d_universal_thresh']

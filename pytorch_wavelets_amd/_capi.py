@@ -61,6 +61,8 @@ PROTOTYPES = {
     'wl_wpt1d_synthesis': (I, [P, P, I, L, I, I, P, P, I, I, I, P]),
     'wl_scat1d_forward': (I, [P, P, P, I, L, I, I, P, I, P, I, C.c_double, I, P]),
     'wl_scat1d_backward': (I, [P, P, P, I, L, I, I, P, I, P, I, C.c_double, I, P]),
+    'wl_shrink1d_forward': (I, [P, P, P, I, L, I, I, P, P, P, P, I, I, I, P]),
+    'wl_shrink1d_backward': (I, [P, P, P, P, P, I, L, I, I, P, P, P, P, I, I, I, P]),
     'wl_wpt2d_analysis':(I, [P, L, I, P, I, L, I, I, I, P, P, P, P, I, I, P]),
     'wl_wpt2d_synthesis': (I, [P, P, I, L, I, I, I, I, I, P, P, P, P, I, I, P]),
     'wl_scat_bwd_level1': (I, [P, P, P, P, I, L, I, I, I, P, I, P, I, I, I, P]),

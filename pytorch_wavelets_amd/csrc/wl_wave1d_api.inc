@@ -1,10 +1,11 @@
 // C ABI of the wave-tile kernels (wl_wave1d.h): the 1-D stationary transform (wl_swt1d.h), the 1-D wavelet packet transform
-// (wl_wpt1d.h) and the 1-D scattering layer (wl_scat1d.h).  Included at the end of wl_dtcwt1d_api.inc, so compiled in the fourth translation unit of the HIP build
+// (wl_wpt1d.h), the 1-D scattering layer (wl_scat1d.h) and the shrinkage of the stationary transform (wl_shrink1d.h).  Included at the end of wl_dtcwt1d_api.inc, so compiled in the fourth translation unit of the HIP build
 // (wl_dtinv_hip.hip) and in the matching unit of the host emulation.
 #include "wl_api_common.h"
 #include "wl_swt1d.h"
 #include "wl_wpt1d.h"
 #include "wl_scat1d.h"
+#include "wl_shrink1d.h"
 
 // the grid of a launch: tiles of `core` positions from -origin on, WL_WAVE1D_WAVES tiles per workgroup
 struct WlWave1dGrid { int core, tiles; int64_t waves, nblocks; };
@@ -101,6 +102,54 @@ extern "C" int wl_swt1d_adjoint(const void* lo, const void* const* his, void* y,
         WL_WAVE1D_BY_TAPS(WlSwt1dAdj, a, g, stream)
     });
 }
+
+// ---- shrinkage of the 1-D stationary transform: analysis, threshold and inverse in one launch (wl_shrink1d.h)
+static int wl_shrink1d_grid(int64_t rows, int n, int J, int L, int dtype, int kind, int origin, WlWave1dGrid& g) {
+    const int rc = wl_wave1d_check(rows, n, J, L, dtype, kind == WL_SHRINK_SOFT || kind == WL_SHRINK_HARD, origin);
+    if (rc != 0) return rc;
+    return wl_wave1d_grid(rows, n, origin, 64 * WL_WAVE1D_V - 2 * (L - 1) * ((1 << J) - 1), g);
+}
+
+#define WL_SHRINK1D_FILL(a, g)                                                                 \
+    a.thr = (const float*)thr;                                                                 \
+    a.h0 = (const float*)h0; a.h1 = (const float*)h1; a.g0 = (const float*)g0; a.g1 = (const float*)g1; \
+    WL_WAVE1D_FILL(a, g, rows, n, J, origin);                                                  \
+    a.kind = kind
+
+extern "C" int wl_shrink1d_forward(const void* x, void* y, const void* thr, int dtype, int64_t rows, int n, int J, const void* h0,
+                                   const void* h1, const void* g0, const void* g1, int L, int kind, int origin, void* stream) {
+    WlWave1dGrid g;
+    const int rc = wl_shrink1d_grid(rows, n, J, L, dtype, kind, origin, g);
+    if (rc != 0) return rc;
+    if (!x || !y || !thr) return WL_ERR_SHAPE;
+    if (!h0 || !h1 || !g0 || !g1) return WL_ERR_TAPS;
+    if (rows == 0) return 0;
+    WL_DISPATCH_FLOAT(dtype, {
+        WlShrink1dFwdArgs<T> a;
+        a.x = (const T*)x; a.y = (T*)y;
+        WL_SHRINK1D_FILL(a, g);
+        WL_WAVE1D_BY_TAPS(WlShrink1dFwd, a, g, stream)
+    });
+}
+
+extern "C" int wl_shrink1d_backward(const void* x, const void* dy, void* dx, const void* thr, void* dthr_part, int dtype, int64_t rows,
+                                    int n, int J, const void* h0, const void* h1, const void* g0, const void* g1, int L, int kind,
+                                    int origin, void* stream) {
+    WlWave1dGrid g;
+    const int rc = wl_shrink1d_grid(rows, n, J, L, dtype, kind, origin, g);
+    if (rc != 0) return rc;
+    if (!x || !dy || !dx || !thr) return WL_ERR_SHAPE;
+    if (!h0 || !h1 || !g0 || !g1) return WL_ERR_TAPS;
+    if (rows == 0) return 0;
+    WL_DISPATCH_FLOAT(dtype, {
+        WlShrink1dBwdArgs<T> a;
+        a.x = (const T*)x; a.dy = (const T*)dy; a.dx = (T*)dx;
+        a.dthr_part = (float*)dthr_part;
+        WL_SHRINK1D_FILL(a, g);
+        WL_WAVE1D_BY_TAPS(WlShrink1dBwd, a, g, stream)
+    });
+}
+#undef WL_SHRINK1D_FILL
 
 #define WL_WPT1D_ENTRY(K, from, to, t0, t1)                                                                                     \
     WlWave1dGrid g;                                                                                                             \

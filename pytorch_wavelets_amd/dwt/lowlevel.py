@@ -791,6 +791,113 @@ def iswt1d(yl, yh, g0, g1, mode='periodic'):
     return ISWT1DMulti.apply(yl, t0, t1, *yh)
 
 
+# ---- shrinkage of the 1-D stationary transform -----------------------------------------------------------------------------------
+# y = iswt1d(lo_J, shrink(hi_j, t_j)) of swt1d(x).  Periodic, four even filters of one length <= 20, J <= 3, not float64: ONE launch
+# per direction of the wave-tile kernels (csrc/wl_shrink1d.h: the coefficients never leave registers, the backward recomputes
+# them); everything else is the composition below with ordinary autograd, which is also the definition.
+class _ShrinkDeclined(Exception):
+    """The launcher declined a call ops.shrink1d_covered let through (a memoised decline, an engine option): swt1d_shrink
+    composes instead."""
+
+
+class SWT1DShrinkF(Function):
+    """``SWT1DShrinkF.apply(x, table, h0, h1, g0, g1, J, kind) -> y``: table = the float32 (J, N, C) thresholds.  One autograd
+    node that saves x and the table; the backward is one launch, which writes the tiles' shares of d table only when the table
+    asks for a gradient.  A forward the launcher declines raises _ShrinkDeclined; a backward it declines differentiates the
+    composition on the saved x and table."""
+
+    @staticmethod
+    def forward(ctx, x, table, h0, h1, g0, g1, J, kind):
+        y = ops.shrink1d_fwd(x, table, h0, h1, g0, g1, J, kind)
+        if y is None:
+            raise _ShrinkDeclined()
+        ctx.save_for_backward(x, table, h0, h1, g0, g1)
+        ctx.geom = (J, kind)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return (None,) * 8
+        x, table, h0, h1, g0, g1 = ctx.saved_tensors
+        J, kind = ctx.geom
+        res = ops.shrink1d_bwd(x, dy, table, h0, h1, g0, g1, J, kind, need_dthr=ctx.needs_input_grad[1])
+        if res is None:
+            with torch.enable_grad():
+                xr, tr = x.detach().requires_grad_(True), table.detach().requires_grad_(True)
+                dx, dtable = torch.autograd.grad(_shrink_composed(xr, tr, h0, h1, g0, g1, J, kind), (xr, tr), dy)
+            return (dx if ctx.needs_input_grad[0] else None, dtable if ctx.needs_input_grad[1] else None) + (None,) * 6
+        dx, part = res
+        dtable = None
+        if part is not None:
+            dtable = part.sum(1).t().reshape(table.shape)          # (rows, tiles, J) -> (J, N, C)
+        return (dx if ctx.needs_input_grad[0] else None, dtable) + (None,) * 6
+
+
+def _shrink_table(thresh, J, N, C, ref):
+    """The thresholds as a (J, N, C) view: 0-d, (J,), or 3-d with every dimension 1 or the size of (J, N, C)."""
+    if not isinstance(thresh, torch.Tensor):
+        thresh = torch.as_tensor(thresh, dtype=torch.float32, device=ref.device)
+    if not thresh.is_floating_point():
+        thresh = thresh.float()
+    ops._same_device(ref, thresh)
+    if thresh.dim() == 1 and thresh.shape[0] == J:
+        thresh = thresh.reshape(J, 1, 1)
+    elif thresh.dim() == 0:
+        thresh = thresh.reshape(1, 1, 1)
+    elif thresh.dim() != 3 or any(s not in (1, full) for s, full in zip(thresh.shape, (J, N, C))):
+        raise ValueError("thresh must be 0-d, ({},) or 3-d with every dimension 1 or that of ({}, {}, {}), not {}".format(
+            J, J, N, C, tuple(thresh.shape)))
+    return thresh.expand(J, N, C)
+
+
+def shrink(w, t, kind='soft'):
+    """Element-wise shrinkage with ordinary autograd: soft sign(w) max(|w| - t, 0), hard w [|w| > t]; hard gives t a zero
+    gradient.  The result has w's dtype."""
+    if kind == 'soft':
+        out = torch.sign(w) * torch.clamp(w.abs() - t, min=0)
+    else:
+        out = w * (w.abs() > t)
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            out = out + 0 * t
+    return out.to(w.dtype)
+
+
+def _shrink_composed(x, table, h0, h1, g0, g1, J, kind):
+    """The definition: swt1d, element-wise shrinkage under table (J, N, C), iswt1d, with ordinary autograd."""
+    lo, his = swt1d(x, h0, h1, 'periodic', J)
+    return iswt1d(lo, [shrink(hi, table[j].unsqueeze(-1), kind) for j, hi in enumerate(his)], g0, g1, 'periodic')
+
+
+def swt1d_shrink(x, h0, h1, g0, g1, thresh, J, kind='soft', mode='periodic'):
+    """Translation-invariant wavelet shrinkage of x (N, C, L) along L: ``iswt1d(lo_J, [shrink(hi_j, t_j)])`` of
+    ``swt1d(x, h0, h1, 'periodic', J)``, soft ``sign(w) max(|w| - t, 0)`` or hard ``w [|w| > t]``, with t_j the threshold of
+    level j for the row's (n, c): `thresh` is 0-d, (J,) or 3-d with every dimension 1 or that of (J, N, C), and is used as given
+    (no clamp).  Differentiable in x and thresh (hard: zeros for thresh).  One launch per direction where the kernels cover
+    the call (ops.shrink1d_covered); otherwise - float64, J > 3, odd, long or unequal filters, ops.SHRINK1D_FUSED off - the
+    composition.  'periodic' and even tap counts only, as the inverse."""
+    h0, h1 = _as_taps(h0, x), _as_taps(h1, x)
+    g0, g1 = _as_syn_taps(g0, x), _as_syn_taps(g1, x)
+    _check_atrous_inverse(mode, h0, h1, g0, g1)
+    if kind not in ops.SHRINK1D_KINDS:
+        raise ValueError("kind must be 'soft' or 'hard', not {!r}".format(kind))
+    _check_swt1d_input(x, 'x')
+    ops._check_tensor(x, 'x')
+    if J < 1:
+        return x
+    N, C = x.shape[:2]
+    table = _shrink_table(thresh, J, N, C, x)
+    if x.numel() == 0:
+        return x.clone()
+    if ops.shrink1d_covered(x, h0, h1, g0, g1, J):
+        try:
+            return SWT1DShrinkF.apply(x, table.to(torch.float32).contiguous(), h0, h1, g0, g1, J, kind)
+        except _ShrinkDeclined:
+            pass
+    return _shrink_composed(x, table, h0, h1, g0, g1, J, kind)
+
+
 class SWTInvMulti(Function):
     """All levels of the inverse stationary transform as ONE autograd node: ``SWTInvMulti.apply(g0_row, g1_row, g0_col, g1_col,
     dilation, *coeffs) -> x`` with coeffs[j] (N,4C,H,W), finest first, level j dilated by dilation * 2**j.  It starts from the ll

@@ -1400,6 +1400,90 @@ def swt1d_adj(lo, his, g0, g1, scale, origin=0):
     return y
 
 
+# ---------------------------------------------------------------------------------------------- shrinkage of the 1-D stationary transform
+SHRINK1D_FUSED = True   # SWT1DShrink forward and backward in one launch each on the wave-tile kernels (csrc/wl_shrink1d.h).  False:
+#                         SWT1DForward, element-wise torch operations, SWT1DInverse and autograd, for A/B measurements and tests.
+SHRINK1D_KINDS = {'soft': 0, 'hard': 1}   # WL_SHRINK_SOFT, WL_SHRINK_HARD
+
+
+def shrink1d_core(L, J):
+    """Positions of a wave's tile the shrinkage kernels store, and what the tiles of a row advance by: the analysis and the
+    inverse behind it eat (L - 1)(2^J - 1) positions on either side."""
+    return WAVE1D_TILE - 2 * (L - 1) * (2 ** J - 1)
+
+
+def shrink1d_covered(x, h0, h1, g0, g1, J):
+    """What the fused route asks: the switch, the element type, four even filters of one length up to 20 taps, 1..3 levels."""
+    L = h0.numel()
+    return (SHRINK1D_FUSED and h1.numel() == L and g0.numel() == L and g1.numel() == L
+            and _wave1d_covered(x, x.shape[-1], L, L, J))
+
+
+def _shrink1d_args(x, thr, taps, nlev, kind):
+    """(rows, n, L) of a launch, or None outside the envelope of the kernels; thr must be the float32 (nlev, rows) table."""
+    L, n = taps[0].numel(), x.shape[-1]
+    if kind not in SHRINK1D_KINDS:
+        raise ValueError("kind must be 'soft' or 'hard', not {!r}".format(kind))
+    if any(t.numel() != L for t in taps) or not _wave1d_covered(x, n, L, L, nlev):
+        return None
+    rows = x.numel() // n
+    if thr.dtype != torch.float32 or thr.numel() != nlev * rows:
+        raise ValueError('shrink1d: the thresholds are %s %s, not float32 with %d x %d elements'
+                         % (tuple(thr.shape), thr.dtype, nlev, rows))
+    _same_device(x, thr)
+    return rows, n, L
+
+
+def shrink1d_fwd(x, thr, h0, h1, g0, g1, nlev, kind='soft', origin=0):
+    """Analysis, shrinkage and inverse of `nlev` (1..3) periodic levels of the 1-D stationary transform along the LAST axis in
+    ONE launch (wl_shrink1d_forward): x (..., n) and thr, float32 (nlev, rows) -> y (..., n).  None when the launcher declines
+    (float64, odd, long or unequal filters, more levels): callers compose.  `origin` (tests) moves the tile seams."""
+    _check_tensor(x, 'x')
+    geom = _shrink1d_args(x, thr, (h0, h1, g0, g1), nlev, kind)
+    if geom is None:
+        return None
+    rows, n, L = geom
+    key = ('shrink1d_fwd', x.device, x.dtype, rows, n, L, nlev)
+    if key in _FUSED_DECLINED:
+        return None
+    x, thr = x.contiguous(), thr.contiguous()
+    t = [_taps(h, x) for h in (h0, h1, g0, g1)]
+    y = torch.empty_like(x)
+    if _declined(key, 'wl_shrink1d_forward', x, x.data_ptr(), y.data_ptr(), thr.data_ptr(), _DTYPES[x.dtype], rows, n, nlev,
+                 t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), L, SHRINK1D_KINDS[kind], int(origin), _stream(x)):
+        return None
+    return y
+
+
+def shrink1d_bwd(x, dy, thr, h0, h1, g0, g1, nlev, kind='soft', need_dthr=True, origin=0):
+    """The backward of shrink1d_fwd in ONE launch (wl_shrink1d_backward), which recomputes the coefficients: x, dy (..., n) and
+    thr -> (dx (..., n), dthr_part): dthr_part, float32 (rows, tiles, nlev), holds each tile's share of the threshold
+    gradients (zeros for 'hard') - the caller sums over tiles -, or is None without `need_dthr` (the launch then gets a null
+    pointer and skips the reduction).  None when the launcher declines."""
+    _check_tensor(x, 'x')
+    _check_tensor(dy, 'dy')
+    _same_device(x, dy)
+    if dy.dtype != x.dtype or dy.shape != x.shape:
+        raise ValueError('shrink1d_bwd: dy %s %s does not belong to x %s %s' % (tuple(dy.shape), dy.dtype, tuple(x.shape), x.dtype))
+    geom = _shrink1d_args(x, thr, (h0, h1, g0, g1), nlev, kind)
+    if geom is None:
+        return None
+    rows, n, L = geom
+    key = ('shrink1d_bwd', x.device, x.dtype, rows, n, L, nlev)
+    if key in _FUSED_DECLINED:
+        return None
+    x, dy, thr = x.contiguous(), dy.contiguous(), thr.contiguous()
+    t = [_taps(h, x) for h in (h0, h1, g0, g1)]
+    dx = torch.empty_like(x)
+    tiles = -(-(n + int(origin)) // shrink1d_core(L, nlev))
+    part = torch.empty((rows, tiles, nlev), dtype=torch.float32, device=x.device) if need_dthr else None
+    if _declined(key, 'wl_shrink1d_backward', x, x.data_ptr(), dy.data_ptr(), dx.data_ptr(), thr.data_ptr(),
+                 part.data_ptr() if need_dthr else None, _DTYPES[x.dtype], rows, n, nlev, t[0].data_ptr(), t[1].data_ptr(),
+                 t[2].data_ptr(), t[3].data_ptr(), L, SHRINK1D_KINDS[kind], int(origin), _stream(x)):
+        return None
+    return dx, part
+
+
 # ---------------------------------------------------------------------------------------------- the 1-D scattering layer
 SCAT1D_FUSED = True   # ScatLayer1D forward and backward in one launch each on the wave-tile kernels (csrc/wl_scat1d.h).  False:
 #                       level 1 of the 1-D DTCWT plus element-wise torch operations and autograd, for A/B measurements and tests.
