@@ -53,7 +53,8 @@ extern "C" {
  *          wl_wpt2d_analysis / wl_wpt2d_synthesis (the 2-D wavelet packet level) likewise; wl_swt1d_analysis / wl_swt1d_adjoint
  *          (the 1-D stationary transform) likewise; wl_wpt1d_analysis / wl_wpt1d_synthesis (the 1-D wavelet packet transform)
  *          likewise; wl_scat1d_forward / wl_scat1d_backward (the 1-D scattering layer) likewise; wl_shrink1d_forward /
- *          wl_shrink1d_backward (shrinkage of the 1-D stationary transform) likewise. */
+ *          wl_shrink1d_backward (shrinkage of the 1-D stationary transform) likewise; wl_swt1d_tapgrad (the tap gradients of the
+ *          1-D stationary transform) likewise. */
 int wl_version(void);
 const char* wl_backend(void);
 
@@ -458,6 +459,21 @@ int wl_shrink1d_forward(const void* x, void* y, const void* thr, int dtype, int6
 int wl_shrink1d_backward(const void* x, const void* dy, void* dx, const void* thr, void* dthr_part, int dtype, int64_t rows, int n,
                          int J, const void* h0, const void* h1, const void* g0, const void* g1, int L, int kind, int origin,
                          void* stream);
+
+/* The gradient of the 1-D stationary transform with respect to its filter taps, in ONE launch on wave tiles
+ * (csrc/wl_swt1d_tapgrad.h; no LDS, no barrier, no atomics).  With d_j = 2^(j-1), everything periodic with period n:
+ *     u_0 = s,  u_j = scale A0_j(k0) u_{j-1}                            (the chain of wl_swt1d_analysis)
+ *     v_J = top,  v_{j-1} = scale (A0_j(k0)^T v_j + A1_j(k1)^T w_j)       (the chain of wl_swt1d_adjoint), w_j = his[j - 1], NULL = zeros
+ *     c0[t] = scale sum_j sum_p u_{j-1}[p + (t - (L/2 - 1)) d_j] v_j[p],   c1[t] = the same with w_j[p],   t = 0 .. L - 1.
+ * (s, top, his, k, scale) = (x, dlo, dhi, h, 1) gives the tap gradients of wl_swt1d_analysis; (dx, lo, hi, g, 1/2) those of
+ * wl_swt1d_adjoint with 1/2 per level (the inverse).  part (float32, rows x tiles x 2 x L with tiles = ceil((n + origin) / core)):
+ * part[((row * tiles + tile) * 2 + b) * L + t] = the share of cb[t] of the tile's core; the caller sums over rows and tiles.
+ * origin: the first tile starts that many positions further left (0; tests move the tile seams with it), below the tile's core
+ * 1024 - max((L/2 - 1)(2^J - 1), (L/2)(2^J - 2)) - (L/2)(2^J - 1).
+ * float32 / float16 / bfloat16, even L <= 20, J = 1..3, ext = 3 (periodic).  WL_ERR_UNSUPPORTED outside that envelope, and the
+ * other codes in the order of wl_swt1d_adjoint: callers compose the chains level by level. */
+int wl_swt1d_tapgrad(const void* s, const void* top, const void* const* his, void* part, int dtype, int64_t rows, int n, int J,
+                     const void* k0, const void* k1, int L, int ext, double scale, int origin, void* stream);
 
 /* ---- single-axis building blocks -------------------------------------------------------------------------------
  * One strided / dilated correlation with boundary extension along the middle axis of a dense (outer, n, inner) tensor:

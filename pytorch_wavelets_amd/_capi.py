@@ -57,6 +57,7 @@ PROTOTYPES = {
     'wl_dtcwt1d_synthesis': (I, [P, I, PP, C.POINTER(I), C.POINTER(I), P, I, I, L, I, I, P, P, I, I, P, P, P, P, I, I, P]),
     'wl_swt1d_analysis': (I, [P, P, PP, I, L, I, I, P, P, I, I, C.c_double, I, P]),
     'wl_swt1d_adjoint': (I, [P, PP, P, I, L, I, I, P, P, I, I, C.c_double, I, P]),
+    'wl_swt1d_tapgrad': (I, [P, P, PP, P, I, L, I, I, P, P, I, I, C.c_double, I, P]),
     'wl_wpt1d_analysis': (I, [P, P, I, L, I, I, P, P, I, I, I, P]),
     'wl_wpt1d_synthesis': (I, [P, P, I, L, I, I, P, P, I, I, I, P]),
     'wl_scat1d_forward': (I, [P, P, P, I, L, I, I, P, I, P, I, C.c_double, I, P]),

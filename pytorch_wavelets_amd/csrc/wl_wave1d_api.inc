@@ -1,11 +1,13 @@
 // C ABI of the wave-tile kernels (wl_wave1d.h): the 1-D stationary transform (wl_swt1d.h), the 1-D wavelet packet transform
-// (wl_wpt1d.h), the 1-D scattering layer (wl_scat1d.h) and the shrinkage of the stationary transform (wl_shrink1d.h).  Included at the end of wl_dtcwt1d_api.inc, so compiled in the fourth translation unit of the HIP build
+// (wl_wpt1d.h), the 1-D scattering layer (wl_scat1d.h), the shrinkage of the stationary transform (wl_shrink1d.h) and the tap
+// gradients of the stationary transform (wl_swt1d_tapgrad.h).  Included at the end of wl_dtcwt1d_api.inc, so compiled in the fourth translation unit of the HIP build
 // (wl_dtinv_hip.hip) and in the matching unit of the host emulation.
 #include "wl_api_common.h"
 #include "wl_swt1d.h"
 #include "wl_wpt1d.h"
 #include "wl_scat1d.h"
 #include "wl_shrink1d.h"
+#include "wl_swt1d_tapgrad.h"
 
 // the grid of a launch: tiles of `core` positions from -origin on, WL_WAVE1D_WAVES tiles per workgroup
 struct WlWave1dGrid { int core, tiles; int64_t waves, nblocks; };
@@ -100,6 +102,27 @@ extern "C" int wl_swt1d_adjoint(const void* lo, const void* const* his, void* y,
         WL_WAVE1D_FILL(a, g, rows, N, J, origin);
         a.scale = (float)scale;
         WL_WAVE1D_BY_TAPS(WlSwt1dAdj, a, g, stream)
+    });
+}
+
+// ---- the tap gradients of the 1-D stationary transform: both chains and the 2 L correlations in one launch (wl_swt1d_tapgrad.h)
+extern "C" int wl_swt1d_tapgrad(const void* s, const void* top, const void* const* his, void* part, int dtype, int64_t rows, int n,
+                                int J, const void* k0, const void* k1, int L, int ext, double scale, int origin, void* stream) {
+    WlWave1dGrid g;
+    int rc = wl_wave1d_check(rows, n, J, L, dtype, ext == WL_EXT_PERIODIC, origin);
+    if (rc == 0) rc = wl_wave1d_grid(rows, n, origin, wl_swt1d_tapgrad_core(L, J), g);
+    if (rc != 0) return rc;
+    if (!s || !top || !his || !part) return WL_ERR_SHAPE;
+    if (!k0 || !k1) return WL_ERR_TAPS;
+    if (rows == 0) return 0;
+    WL_DISPATCH_FLOAT(dtype, {
+        WlSwt1dTapGradArgs<T> a;
+        a.s = (const T*)s; a.top = (const T*)top; a.part = (float*)part;
+        for (int l = 0; l < WL_WAVE1D_MAXJ; ++l) a.hi[l] = l < J ? (const T*)his[l] : nullptr;
+        a.k0 = (const float*)k0; a.k1 = (const float*)k1;
+        WL_WAVE1D_FILL(a, g, rows, n, J, origin);
+        a.scale = (float)scale;
+        WL_WAVE1D_BY_TAPS(WlSwt1dTapGrad, a, g, stream)
     });
 }
 

@@ -715,13 +715,73 @@ def _swt1d_adjoint(lo, his, g0, g1, ext, ns, scale=1.0):
     return lo
 
 
+# ---- the gradients of the filter taps --------------------------------------------------------------------------------------------
+# Periodic, even L.  With d_j = 2^(j-1), a signal s, a top v_J, highs w_j (None = zeros), taps k and the per-level scale sigma:
+#     u_0 = s, u_j = sigma A0_j(k0) u_{j-1};        v_{j-1} = sigma (A0_j(k0)^T v_j + A1_j(k1)^T w_j)
+#     c0[t] = sigma sum_j sum_p u_{j-1}[p + (t - (L/2 - 1)) d_j] v_j[p],        c1[t] = the same with w_j[p]
+# (x, dlo, dhi, h, 1) gives (dh0, dh1) of SWT1DMulti, (dx, lo, hi, g, 1/2) gives (dg0, dg1) of ISWT1DMulti.  Up to three levels of
+# float32 / float16 / bfloat16 data are ONE launch (csrc/wl_swt1d_tapgrad.h); everything else is the composition below, which is
+# also the definition.
+def _check_tap_grad_envelope(ext, *taps):
+    if ext != ops.EXT_PERIODIC:
+        raise ValueError("the filter taps of the stationary transform have a gradient in mode 'periodic' only")
+    for t in taps:
+        if t.numel() % 2:
+            raise ValueError("the gradient of the filter taps needs an even number of taps, not {}".format(t.numel()))
+    if taps[0].numel() != taps[1].numel():
+        raise ValueError("the gradient of the filter taps needs two filters of one length, not {} and {}".format(
+            taps[0].numel(), taps[1].numel()))
+
+
+def _swt1d_tapgrad_composed(s, top, his, k0, k1, scale):
+    """The definition: both chains one level at a time on corr1d / corr1d_adj, and per level and tap a rolled product summed in
+    float64 on the device -> (c0, c1), float64 (L,)."""
+    J, L, n = len(his), k0.numel(), s.shape[-1]
+    ext = ops.EXT_PERIODIC
+    us = [s]
+    for j in range(J - 1):
+        K, start = _atrous_geom(n, L, 2 ** j)
+        lo, _ = ops.corr1d(us[-1], -1, k0, k1, K, start, 1, 2 ** j, ext)
+        us.append(lo.mul_(scale) if scale != 1.0 else lo)
+    c0 = torch.zeros(L, dtype=torch.float64, device=s.device)
+    c1 = torch.zeros(L, dtype=torch.float64, device=s.device)
+    v = top
+    for j in range(J - 1, -1, -1):
+        d, w = 2 ** j, his[j]
+        v64 = v.double()
+        w64 = None if w is None else w.double()
+        for t in range(L):
+            u64 = torch.roll(us[j], -(t - (L // 2 - 1)) * d, -1).double()
+            c0[t] += (u64 * v64).sum()
+            if w64 is not None:
+                c1[t] += (u64 * w64).sum()
+        if j:
+            v = ops.corr1d_adj(v, w, -1, k0, None if w is None else k1, n, _atrous_geom(n, L, d)[1], d, ext, scale)
+    return c0 * scale, c1 * scale
+
+
+def _swt1d_tapgrad(s, top, his, k0, k1, scale):
+    """(c0, c1) shaped and typed like k0 / k1: one launch where the kernel covers the call, the composition otherwise."""
+    res = None
+    if len(his) <= ops.SWT1D_MAXJ:
+        res = ops.swt1d_tapgrad(s, top, his, k0, k1, scale)
+    if res is None:
+        res = _swt1d_tapgrad_composed(s, top, his, k0, k1, scale)
+    return res[0].to(k0.dtype).reshape(k0.shape), res[1].to(k1.dtype).reshape(k1.shape)
+
+
 class SWT1DMulti(Function):
     """``SWT1DMulti.apply(x, h0, h1, ext, J) -> (lo, hi_1 .. hi_J)``: all levels of the 1-D stationary analysis as ONE autograd
-    node.  Backward = the transposed cascade with the same taps."""
+    node.  Backward = the transposed cascade with the same taps; a tap tensor that asks for a gradient ('periodic', even L) gets
+    it from _swt1d_tapgrad, for which x is saved as well."""
 
     @staticmethod
     def forward(ctx, x, h0, h1, ext, J):
-        ctx.save_for_backward(h0, h1)
+        ctx.taps_learn = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        if ctx.taps_learn:
+            ctx.save_for_backward(h0, h1, x)
+        else:
+            ctx.save_for_backward(h0, h1)
         lo, his, ns = _swt1d_analysis(x, h0, h1, ext, J)
         ctx.geom = (ext, ns)
         return (lo,) + tuple(his)
@@ -729,33 +789,53 @@ class SWT1DMulti(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dlo, *dhis):
-        dx = None
+        dx = dh0 = dh1 = None
+        ext, ns = ctx.geom
         if ctx.needs_input_grad[0]:
-            h0, h1 = ctx.saved_tensors
-            ext, ns = ctx.geom
+            h0, h1 = ctx.saved_tensors[:2]
             dx = _swt1d_adjoint(dlo, list(dhis), h0, h1, ext, ns)
-        return dx, None, None, None, None
+        if ctx.taps_learn:
+            h0, h1, x = ctx.saved_tensors
+            dh0, dh1 = _swt1d_tapgrad(x, dlo, list(dhis), h0, h1, 1.0)
+            dh0 = dh0 if ctx.needs_input_grad[1] else None
+            dh1 = dh1 if ctx.needs_input_grad[2] else None
+        return dx, dh0, dh1, None, None
 
 
 class ISWT1DMulti(Function):
     """``ISWT1DMulti.apply(lo, g0, g1, *his) -> x``: all levels of the inverse 1-D stationary transform, coarsest first
     lo_{j-1} = 1/2 (A_0(g)^T lo_j + A_1(g)^T hi_j), as ONE autograd node; his finest first, None = zeros.  Backward = 1/2 per
-    level of the analysis cascade with the synthesis taps."""
+    level of the analysis cascade with the synthesis taps; a tap tensor that asks for a gradient gets it from _swt1d_tapgrad, for
+    which lo and the highs that are present are saved as well."""
 
     @staticmethod
     def forward(ctx, lo, g0, g1, *his):
-        ctx.save_for_backward(g0, g1)
+        ctx.taps_learn = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         ctx.present = [h is not None for h in his]
+        if ctx.taps_learn:
+            ctx.save_for_backward(g0, g1, lo, *[h for h in his if h is not None])
+        else:
+            ctx.save_for_backward(g0, g1)
         n = lo.shape[-1]
         return _swt1d_adjoint(lo, list(his), g0, g1, ops.EXT_PERIODIC, [n] * len(his), 0.5)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dx):
-        g0, g1 = ctx.saved_tensors
-        dlo, dhis, _ = _swt1d_analysis(dx, g0, g1, ops.EXT_PERIODIC, len(ctx.present), 0.5)
-        # (level j's bands carry the factors of the levels above it as well: they were applied on the way down)
-        return (dlo, None, None) + tuple(d if p else None for d, p in zip(dhis, ctx.present))
+        g0, g1 = ctx.saved_tensors[:2]
+        grads = (None,) * len(ctx.present)
+        dlo = dg0 = dg1 = None
+        if any(ctx.needs_input_grad[:1] + ctx.needs_input_grad[3:]) or not ctx.taps_learn:
+            dlo, dhis, _ = _swt1d_analysis(dx, g0, g1, ops.EXT_PERIODIC, len(ctx.present), 0.5)
+            # (level j's bands carry the factors of the levels above it as well: they were applied on the way down)
+            grads = tuple(d if p else None for d, p in zip(dhis, ctx.present))
+        if ctx.taps_learn:
+            kept = iter(ctx.saved_tensors[3:])
+            his = [next(kept) if p else None for p in ctx.present]
+            dg0, dg1 = _swt1d_tapgrad(dx, ctx.saved_tensors[2], his, g0, g1, 0.5)
+            dg0 = dg0 if ctx.needs_input_grad[1] else None
+            dg1 = dg1 if ctx.needs_input_grad[2] else None
+        return (dlo, dg0, dg1) + grads
 
 
 def _check_swt1d_input(t, name):
@@ -766,19 +846,24 @@ def _check_swt1d_input(t, name):
 def swt1d(x, h0, h1, mode='periodic', J=1):
     """J levels of the 1-D stationary (undecimated) transform of x (N, C, L) along L: (yl, [yh_1 .. yh_J]) finest first, every
     tensor (N, C, L).  Level j is afb1d_atrous with dilation 2**(j-1) on the previous lowpass (stored taps, the six pad modes of
-    afb1d_atrous; any other mode raises its ValueError).  Differentiable in x."""
+    afb1d_atrous; any other mode raises its ValueError).  Differentiable in x, and in tap tensors that require a gradient
+    ('periodic', two filters of one even length: ValueError otherwise)."""
     if mode not in _ATROUS_EXT:
         raise ValueError("Unkown pad type: {}".format(mode))
     _check_swt1d_input(x, 'x')
     if J < 1:
         return x, []
-    outs = SWT1DMulti.apply(x, _as_taps(h0, x), _as_taps(h1, x), _ATROUS_EXT[mode], J)
+    h0, h1 = _as_taps(h0, x), _as_taps(h1, x)
+    if torch.is_grad_enabled() and (h0.requires_grad or h1.requires_grad):
+        _check_tap_grad_envelope(_ATROUS_EXT[mode], h0, h1)
+    outs = SWT1DMulti.apply(x, h0, h1, _ATROUS_EXT[mode], J)
     return outs[0], list(outs[1:])
 
 
 def iswt1d(yl, yh, g0, g1, mode='periodic'):
     """The inverse of swt1d: yl (N, C, L) and yh = [finest .. coarsest] (None = zeros) -> x (N, C, L), per level, coarsest first,
-    lo_{j-1} = 1/2 (A_0(g)^T lo_j + A_1(g)^T hi_j) - the 1-D case of sfb1d_atrous.  'periodic' and even tap counts only."""
+    lo_{j-1} = 1/2 (A_0(g)^T lo_j + A_1(g)^T hi_j) - the 1-D case of sfb1d_atrous.  'periodic' and even tap counts only.
+    Differentiable in yl, yh and in tap tensors that require a gradient (two filters of one length)."""
     t0, t1 = _as_syn_taps(g0, yl), _as_syn_taps(g1, yl)
     _check_atrous_inverse(mode, t0, t1)
     _check_swt1d_input(yl, 'yl')
@@ -788,6 +873,8 @@ def iswt1d(yl, yh, g0, g1, mode='periodic'):
             raise ValueError("yl is {} and a level of yh is {}".format(tuple(yl.shape), tuple(h.shape)))
     if not yh:
         return yl
+    if torch.is_grad_enabled() and (t0.requires_grad or t1.requires_grad):
+        _check_tap_grad_envelope(ops.EXT_PERIODIC, t0, t1)
     return ISWT1DMulti.apply(yl, t0, t1, *yh)
 
 
@@ -875,8 +962,8 @@ def swt1d_shrink(x, h0, h1, g0, g1, thresh, J, kind='soft', mode='periodic'):
     ``swt1d(x, h0, h1, 'periodic', J)``, soft ``sign(w) max(|w| - t, 0)`` or hard ``w [|w| > t]``, with t_j the threshold of
     level j for the row's (n, c): `thresh` is 0-d, (J,) or 3-d with every dimension 1 or that of (J, N, C), and is used as given
     (no clamp).  Differentiable in x and thresh (hard: zeros for thresh).  One launch per direction where the kernels cover
-    the call (ops.shrink1d_covered); otherwise - float64, J > 3, odd, long or unequal filters, ops.SHRINK1D_FUSED off - the
-    composition.  'periodic' and even tap counts only, as the inverse."""
+    the call (ops.shrink1d_covered); otherwise - float64, J > 3, odd, long or unequal filters, ops.SHRINK1D_FUSED off, a tap
+    tensor that requires a gradient - the composition.  'periodic' and even tap counts only, as the inverse."""
     h0, h1 = _as_taps(h0, x), _as_taps(h1, x)
     g0, g1 = _as_syn_taps(g0, x), _as_syn_taps(g1, x)
     _check_atrous_inverse(mode, h0, h1, g0, g1)
@@ -890,7 +977,9 @@ def swt1d_shrink(x, h0, h1, g0, g1, thresh, J, kind='soft', mode='periodic'):
     table = _shrink_table(thresh, J, N, C, x)
     if x.numel() == 0:
         return x.clone()
-    if ops.shrink1d_covered(x, h0, h1, g0, g1, J):
+    # (filters that are learned: the composition, whose two transform nodes have the tap gradients - the fused kernels have none)
+    taps_learn = torch.is_grad_enabled() and any(t.requires_grad for t in (h0, h1, g0, g1))
+    if not taps_learn and ops.shrink1d_covered(x, h0, h1, g0, g1, J):
         try:
             return SWT1DShrinkF.apply(x, table.to(torch.float32).contiguous(), h0, h1, g0, g1, J, kind)
         except _ShrinkDeclined:

@@ -9,7 +9,7 @@ import torch.nn as nn
 
 from . import lowlevel
 from .. import filters
-from .swt1d import SWT1DForward
+from .swt1d import SWT1DForward, _register_taps, _taps_form
 
 
 def _resolve_bank(wave):
@@ -31,18 +31,17 @@ class SWT1DShrink(nn.Module):
     ``sign(w) max(|w| - t, 0)`` or hard ``w [|w| > t]`` shrinkage.  `thresh` is 0-d, (J,) or 3-d with every dimension 1 or that
     of (J, N, C); it is an ``nn.Parameter`` with `learn`, a buffer otherwise, and an argument of the call overrides it.  It is used
     as given: nothing clamps a learned threshold that turns negative.  The gradient reaches x and the thresholds (hard: zeros).
-    'periodic' and even tap counts only (ValueError otherwise, as SWT1DInverse); J = 0 returns x."""
+    'periodic' and even tap counts only (ValueError otherwise, as SWT1DInverse); J = 0 returns x.  With `learn_filters` the four
+    taps are ``nn.Parameter``s under the buffers' names and the gradient reaches them too: the call then runs SWT1DForward,
+    element-wise shrinkage and SWT1DInverse, whose nodes have the tap gradients (the one-launch kernels have none)."""
 
-    def __init__(self, J=1, wave='db1', thresh=0.0, kind='soft', learn=False, mode='periodic'):
+    def __init__(self, J=1, wave='db1', thresh=0.0, kind='soft', learn=False, mode='periodic', learn_filters=False):
         super().__init__()
         if kind not in ('soft', 'hard'):
             raise ValueError("kind must be 'soft' or 'hard', not {!r}".format(kind))
         h0, h1, g0, g1 = _resolve_bank(wave)
         ana, syn = lowlevel.prep_filt_afb1d(h0, h1), lowlevel.prep_filt_sfb1d(g0, g1)
-        self.register_buffer('h0', ana[0])
-        self.register_buffer('h1', ana[1])
-        self.register_buffer('g0', syn[0])
-        self.register_buffer('g1', syn[1])
+        _register_taps(self, ('h0', 'h1', 'g0', 'g1'), tuple(ana[:2]) + tuple(syn[:2]), learn_filters)
         t = torch.as_tensor(thresh, dtype=torch.float32).clone()
         if learn:
             self.thresh = nn.Parameter(t)
@@ -57,7 +56,7 @@ class SWT1DShrink(nn.Module):
                                      self.kind, self.mode)
 
     def extra_repr(self):
-        return "J={}, kind='{}', learn={}".format(self.J, self.kind, isinstance(self.thresh, nn.Parameter))
+        return "J={}, kind='{}', learn={}, taps={}".format(self.J, self.kind, isinstance(self.thresh, nn.Parameter), _taps_form(self.h0))
 
 
 def swt1d_universal_thresh(x, wave='db1', J=1):

@@ -1400,6 +1400,57 @@ def swt1d_adj(lo, his, g0, g1, scale, origin=0):
     return y
 
 
+SWT1D_TAPGRAD_FUSED = True   # the tap gradients of the 1-D stationary transform in one launch on the wave-tile kernels
+#                              (csrc/wl_swt1d_tapgrad.h).  False: lowlevel's composition - the chains level by level and rolled
+#                              products summed in float64 -, for A/B measurements and tests.
+
+
+def swt1d_tapgrad_core(L, J):
+    """Positions of a wave's tile whose products the tap-gradient kernel sums, and what the tiles of a row advance by: the
+    analysis chain and the adjoint chain eat max((L/2 - 1)(2^J - 1), (L/2)(2^J - 2)) positions in front and (L/2)(2^J - 1) behind."""
+    return WAVE1D_TILE - max((L // 2 - 1) * (2 ** J - 1), (L // 2) * (2 ** J - 2)) - (L // 2) * (2 ** J - 1)
+
+
+def swt1d_tapgrad(s, top, his, k0, k1, scale, origin=0):
+    """The tap gradients of len(his) (1..3) periodic levels of the 1-D stationary transform along the LAST axis in ONE launch
+    (wl_swt1d_tapgrad): s, top (..., n), his = [finest .. coarsest] (None = zeros), the taps k0 / k1 and the per-level scale ->
+    (c0, c1), float32 (L,) each, with u_0 = s, u_j = scale A0_j(k0) u_{j-1}, v_J = top, v_{j-1} = scale (A0_j(k0)^T v_j +
+    A1_j(k1)^T w_j) and d_j = 2^(j-1):
+        c0[t] = scale sum_j sum_p u_{j-1}[p + (t - (L/2 - 1)) d_j] v_j[p],      c1[t] = the same with w_j[p].
+    (s, top, his, k, scale) = (x, dlo, dhi, h, 1): the gradients of swt1d_fwd's taps; (dx, lo, hi, g, 1/2): those of swt1d_adj's
+    with 1/2 per level.  The launch writes every tile's share, float32 (rows, tiles, 2, L), which is summed over rows and tiles
+    in float64.  None when the launcher declines (float64, odd or long filters, more levels, the switch): callers compose.
+    `origin` (tests) moves the tile seams."""
+    _check_tensor(s, 's')
+    _check_tensor(top, 'top')
+    _same_device(s, top)
+    J, L, n = len(his), k0.numel(), s.shape[-1]
+    if top.dtype != s.dtype or top.shape != s.shape:
+        raise ValueError('swt1d_tapgrad: top %s %s does not belong to s %s %s' % (tuple(top.shape), top.dtype, tuple(s.shape), s.dtype))
+    if not SWT1D_TAPGRAD_FUSED or not _swt1d_covered(s, L, k1.numel(), J):
+        return None
+    for h in his:
+        if h is not None:
+            _check_tensor(h, 'his')
+            _same_device(s, h)
+            if h.dtype != s.dtype or h.shape != s.shape:
+                return None
+    rows = s.numel() // n
+    key = ('swt1d_tapgrad', s.device, s.dtype, rows, n, L, J)
+    if key in _FUSED_DECLINED:
+        return None
+    s, top = s.contiguous(), top.contiguous()
+    his = [None if h is None else h.contiguous() for h in his]
+    t0, t1 = _taps(k0, s), _taps(k1, s)
+    tiles = -(-(n + int(origin)) // swt1d_tapgrad_core(L, J))
+    part = torch.empty((rows, tiles, 2, L), dtype=torch.float32, device=s.device)
+    if _declined(key, 'wl_swt1d_tapgrad', s, s.data_ptr(), top.data_ptr(), _ptr_array(his), part.data_ptr(), _DTYPES[s.dtype], rows,
+                 n, J, t0.data_ptr(), t1.data_ptr(), L, EXT_PERIODIC, float(scale), int(origin), _stream(s)):
+        return None
+    c = part.sum((0, 1), dtype=torch.float64).to(torch.float32)
+    return c[0], c[1]
+
+
 # ---------------------------------------------------------------------------------------------- shrinkage of the 1-D stationary transform
 SHRINK1D_FUSED = True   # SWT1DShrink forward and backward in one launch each on the wave-tile kernels (csrc/wl_shrink1d.h).  False:
 #                         SWT1DForward, element-wise torch operations, SWT1DInverse and autograd, for A/B measurements and tests.
