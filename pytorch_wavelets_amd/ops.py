@@ -8,7 +8,8 @@ import torch
 from . import _lib
 
 _DTYPES = {torch.float32: 0, torch.float16: 1, torch.float64: 2, torch.bfloat16: 3}   # bfloat16 takes the float16 kernels
-_TEST_BACKEND = None   # set ONLY by tests/emu_backend.py (host emulation of the kernel sources)
+_TEST_BACKEND = None   # set ONLY by tests: tests/emu_backend.py (host emulation of the kernel sources) and the recording stub of
+                       # tests/_ask_cases.py (no kernel at all: it lists what the wrappers below ask the engine for)
 
 
 def _backend():
@@ -280,7 +281,9 @@ def _hinted_taps(bufs, ref, L, syn):
     ent = cache.get(key) if cache is not None else None
     if ent is None:
         taps = tuple(_taps(b, ref) for b in bufs)
-        scratch = _new_tap_scratch(ref.device) if L >= min(ROWS_LATTICE_MIN, IROWS_LATTICE_MIN) and (STRIP_LATTICE or ROWS_LATTICE) else None
+        # (8 taps: the shortest filter any launcher runs the lattice on - the smaller of WL_ROWS_LAT_MIN, csrc/wl_rows_api.inc, and
+        # WL_IROWS_LAT_MIN, csrc/wl_idwt_rows.h)
+        scratch = _new_tap_scratch(ref.device) if L >= 8 else None
         ent = [taps, scratch, ctypes.c_int(0)]
         if cache is not None:
             cache[key] = ent
@@ -421,32 +424,33 @@ def afb2d_fused(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, nlev, strips=None, whol
     # (csrc/wl_lattice.h): the only fused form of 14, 16 and 20 taps.
     qmf, same = current_hints()
     # (periodization with 12 taps: its odd-cell instantiations are the lattice variant and the two-bank direct form, which spills)
-    lattice = (same and qmf and ROWS_LATTICE and L in (8, 10, 12, 14, 16, 18, 20) and L >= ROWS_LATTICE_MIN
+    # (from 10 taps on: WL_ROWS_LAT_MIN of csrc/wl_rows_api.inc)
+    lattice = (same and qmf and L in (10, 12, 14, 16, 18, 20)
                and (L > 12 or x.numel() >= LATTICE_MIN_ELEMS or (mode == 2 and L == 12)))
     # (float16- or bfloat16-ROUNDED 20-tap banks - the buffers of a `.half()` / bfloat16 module - are no orthogonal pair to within the lattice's tolerance (residue 9e-4,
     # csrc/wl_lattice.h): the examination rejects them and the armed two-bank 20-tap kernel, which spills, would do the work - 0.70 ms against
-    # 0.32 on the strip kernels for 512x1x512^2 J = 2, tools/gpu_r6_per.py deep)
+    # 0.32 on the strip kernels for 512x1x512^2 J = 2, tools/gpu_r6_per.py deep - the script: in the history up to cf61189)
     if L == 20 and h_w_lo.element_size() == 2 and strips == 0:      # (the engine's policy; a forced launch is taken)
         return None
     if (x.dtype == torch.float64 or nlev < 1 or nlev > 3 or h_h_lo.numel() != L or L % 2 or (L > 12 and not lattice)
-            or (nlev > 1 and mode not in (0, 1, 2, 4)) or x.numel() == 0 or (mode == 2 and not ROWS_PER and (nlev > 1 or L % 4 == 0))
+            or (nlev > 1 and mode not in (0, 1, 2, 4)) or x.numel() == 0
             or (strips == 0 and 8 * N * C < 3 * _num_cus(x.device)) or strips > 2):
         return None
     # rows as whole 16-byte pieces: a dense x whose width is one, or a row-padded view (the ll that afb2d_stream(pad_ll=True) /
     # afb2d(pad_ll=True) return: any width, the pitch a whole number of pieces and wide enough for the row's last piece)
     es = x.element_size()
     # float32 rows of 2-3 KiB (three pieces per row, round 5): two and more levels per launch, or a one-level transform.  A single
-    # level of a longer pyramid stays with the strip kernel (tools/gpu_r5v.py, same process: 128x3x768^2 J = 3 as strip + two fused levels
+    # level of a longer pyramid stays with the strip kernel (tools/gpu_r5v.py - in the history up to cf61189 -, same process: 128x3x768^2 J = 3 as strip + two fused levels
     # 0.438 ms, as fused + strip + fused 0.464; the last level of 64x3x1024^2 J = 2 on the padded ll 0.465 against 0.456 on the strip kernel)
     # periodization, float16, 12 / 16 / 20 taps (the odd-cell instantiations of the long filters): the strip kernels - tuned on config 5, two / four
-    # planes per workgroup - are ahead (tools/gpu_r6_per.py deep, same process: 512x1x512^2 db8 J = 2 0.188 ms on two strip launches, 0.216
+    # planes per workgroup - are ahead (tools/gpu_r6_per.py deep, same process, script as above: 512x1x512^2 db8 J = 2 0.188 ms on two strip launches, 0.216
     # fused; J = 1 0.141 / 0.182; db6 0.176 / 0.186; config 5 2.45 / 2.49); float32 (db8 0.294 / 0.245) and 8 taps (0.165 / 0.168; three
     # levels 0.166 / 0.136) stay here
     if mode == 2 and es == 2 and L % 4 == 0 and L >= 12:
         return None
     # ... and rows of exactly 2 KiB (round 6: config 5's 1024-column float16 level, which has more columns than the workgroup has compute
-    # waves for two levels; tools/gpu_r6_per.py: the transform 2.51 ms with that level on the strip kernel, 2.68 on the fused one)
-    if (W * es > 2048 and not ROWS_3KIB) or (W * es >= 2048 and nlev < 2 and not whole):
+    # waves for two levels; tools/gpu_r6_per.py, as above: the transform 2.51 ms with that level on the strip kernel, 2.68 on the fused one)
+    if W * es >= 2048 and nlev < 2 and not whole:
         return None
     x, x_ps, x_rs = _planes(x)
     if (x_rs * es) % 16 or (x_ps * es) % 16 or x.data_ptr() % 16 or (W * es + 15) // 16 * 16 > x_rs * es:
@@ -533,7 +537,8 @@ def sfb2d_fused(yl, yh, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, strips=None):
     es = yl.element_size()
     # (hints as in afb2d_fused: with "same banks" and "quadrature-mirror highpass" 10-20 taps run the lattice variant of the kernel)
     qmf, same = current_hints()
-    lattice = (same and qmf and ROWS_LATTICE and L in (8, 10, 12, 14, 16, 18, 20) and L >= IROWS_LATTICE_MIN
+    # (from 8 taps on: WL_IROWS_LAT_MIN of csrc/wl_idwt_rows.h - the metric's inverse: -6 %)
+    lattice = (same and qmf and L in (8, 10, 12, 14, 16, 18, 20)
                and (L > 12 or (nlev >= 1 and yh[0] is not None and yh[0].dim() == 5
                                and 4 * yh[0].shape[3] * yh[0].shape[4] * N * C >= (LATTICE_MIN_ELEMS if nlev == 1 else min(LATTICE_MIN_ELEMS, LATTICE_MIN_ELEMS_ML)))))
     # float16 data, 10 taps and more: the fused synthesis reads its coefficients one 2-byte element at a time and converts each - the per-level strip /
@@ -544,10 +549,10 @@ def sfb2d_fused(yl, yh, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, strips=None):
     per = mode == 2          # periodization (round 6): every level exactly twice the level above, all 2K outputs kept (the PER instantiations)
     if per and not IROWS_PER:
         return None
-    if per and strips == 0 and IROWS_PER_POLICY and nlev >= 1 and yh[0] is not None and yh[0].dim() == 5:
+    if per and strips == 0 and nlev >= 1 and yh[0] is not None and yh[0].dim() == 5:
         # The periodized loader brings the coefficients in ROW by row (rows that carry their wrapped cells), one LDS-DMA instruction per KiB or part
         # of one: it pays where the finest level's rows fill those instructions and the planes fill the chip.  Same-process A/B against the per-level
-        # ladder (tools/gpu_r6_iper.py, profiles/r06g_*): 128x3x512^2 J=3 db4 0.230 -> 0.175 ms, db2 0.226 -> 0.164, 448^2 0.191 -> 0.143, 384^2 0.136 -> 0.118,
+        # ladder (tools/gpu_r6_iper.py - in the history up to cf61189 -, profiles/r06g_*): 128x3x512^2 J=3 db4 0.230 -> 0.175 ms, db2 0.226 -> 0.164, 448^2 0.191 -> 0.143, 384^2 0.136 -> 0.118,
         # 512x3x512^2 0.848 -> 0.700; behind it: 256-column planes (+20-31 %), 144 planes (+23 %), 16-20 taps (0 to +6 %), float16 from 6 taps on (db4 +52 %)
         ow0 = 2 * yh[0].shape[4]
         if (L > 12 or N * C < _num_cus(yl.device) or (es == 4 and ow0 < 320)
@@ -597,9 +602,6 @@ def sfb2d_fused(yl, yh, g_w_lo, g_w_hi, g_h_lo, g_h_hi, mode, strips=None):
 # compute wave of its workgroups a plane's strip (several planes per workgroup, round 5), workgroups for every CU in both cases.
 STRIP_MINW = 128
 TAP_SCRATCH_FLOATS = 16   # WL_TAP_SCRATCH_FLOATS of csrc/wl_lattice.h
-STRIP_LATTICE = True      # hinted strip launches of 12 taps and more run the lattice variant (False: the QMF variant; A/B measurements)
-ROWS_LATTICE = True       # hinted fused analysis launches of 10-20 taps run the lattice variant (False: A/B measurements; 14-20 taps then go level by level)
-ROWS_LATTICE_MIN = 10     # WL_ROWS_LAT_MIN of csrc/wl_rows_api.inc (8 in the A/B build that tries the lattice on the metric's kernel)
 # Up to 12 taps the direct-form fused kernels exist too, and the lattice launch carries two short extra launches (the examination of the
 # banks ~5 us, the armed fallback ~5 us): it pays from about 40 M elements on (128x3x512x512 = 100 M: inverse -6 % at 8 taps, -15 % at 12;
 # 128x3x224x224 = 19 M: the extra launches are 15 % of a 65 us transform).  From 14 taps on the lattice is the only fused form.
@@ -607,15 +609,8 @@ LATTICE_MIN_ELEMS = 40000000
 # ... two and three synthesis levels in one launch run long enough for the lattice earlier (tools/gpu_r5w.py, 8 taps, same box: 128x3x224^2 J = 2 / 3
 # 0.064 / 0.057 -> 0.057 / 0.049 ms, 128x3x256^2 0.081 / 0.080 -> 0.071 / 0.069, 96x3x299^2 0.082 / 0.098 -> 0.067 / 0.081; at 64x3x224^2 - 10 M - it loses)
 LATTICE_MIN_ELEMS_ML = 16000000
-IROWS_LATTICE_MIN = 8     # WL_IROWS_LAT_MIN of csrc/wl_idwt_rows.h: the fused synthesis takes the lattice from 8 taps on (the metric's inverse: -6 %)
-
-
 IROWS_F16_MAXL = 8      # longest filter the fused synthesis takes on float16 data under the engine's policy (99: A/B measurements)
-IROWS_PER_POLICY = True # (False: A/B measurements - the fused periodized synthesis whatever the shape)
 IROWS_PER = True        # round 6: periodization on the fused synthesis kernel (False: A/B measurements)
-ROWS_PER = True         # round 6: several periodization levels per fused analysis launch, and its odd-cell tap counts (L % 4 == 0) at all (False: A/B measurements)
-ROWS_3KIB = True        # float32 rows of 2-3 KiB on the fused analysis kernel (three 1 KiB pieces per row; False: A/B measurements)
-PAD_ODD_LL = True    # an inner-level ll of the strip kernel whose rows are no whole 16-byte pieces is written at a padded row pitch (A/B: False)
 
 
 def afb2d_stream(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, force=False, pad_ll=False):
@@ -700,7 +695,7 @@ def afb2d_best(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, pad_ll=False, more_level
         res = afb2d_small(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, 1)
         if res is not None:
             return res[0], res[1][0]
-    res = afb2d_stream(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, force=STREAM_FORCE, pad_ll=more_levels and PAD_ODD_LL)
+    res = afb2d_stream(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, force=STREAM_FORCE, pad_ll=more_levels)
     return res if res is not None else afb2d(x, h_w_lo, h_w_hi, h_h_lo, h_h_hi, mode, pad_ll=pad_ll)
 
 
@@ -1539,8 +1534,8 @@ def shrink1d_bwd(x, dy, thr, h0, h1, g0, g1, nlev, kind='soft', need_dthr=True, 
 SCAT1D_FUSED = True   # ScatLayer1D forward and backward in one launch each on the wave-tile kernels (csrc/wl_scat1d.h).  False:
 #                       level 1 of the 1-D DTCWT plus element-wise torch operations and autograd, for A/B measurements and tests.
 SCAT1D_PAIRS = ((5, 7), (5, 3), (13, 19), (9, 7))   # (L0, L1) the kernels are instantiated for: near_sym_a, legall, near_sym_b, antonini
-SCAT1D_MIN_LEN = 0    # rows shorter than this take the composition.  One wave serves one row, but the fused route still wins 3.7x
-#                       at rows of 64 samples, the shortest measured: none do.
+# (no row is too short for the fused route: one wave serves one row, but it still wins 3.7x at rows of 64 samples, the shortest
+# measured - DESIGN.md 4.30)
 
 
 def scat1d_core(L0, L1):
@@ -1550,9 +1545,9 @@ def scat1d_core(L0, L1):
 
 
 def scat1d_covered(x, h0o, h1o):
-    """What the fused route asks: the switch, the element type, an instantiated tap pair, a row the policy sends there."""
+    """What the fused route asks: the switch, the element type, an instantiated tap pair, a row the kernels can index."""
     return (SCAT1D_FUSED and x.dtype != torch.float64 and (h0o.numel(), h1o.numel()) in SCAT1D_PAIRS and x.numel() != 0
-            and SCAT1D_MIN_LEN <= x.shape[-1] < 1 << 29)
+            and x.shape[-1] < 1 << 29)
 
 
 def scat1d_fwd(x, h0o, h1o, magbias, save, origin=0):

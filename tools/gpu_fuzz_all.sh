@@ -8,7 +8,6 @@ run gpu_dtcwt_fuzz 11 60 2
 run gpu_round4_fuzz 300 "" 1
 run gpu_round5_fuzz 300 "" 1
 run gpu_round5b_fuzz 240 "" 2
-run gpu_round6_fuzz 300 "" 2
 run gpu_round6b_fuzz 200 "" 2
 run gpu_round6c_fuzz 6 80 2
 run gpu_narrow_dtcwt_fuzz 60 "" 1

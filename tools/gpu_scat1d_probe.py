@@ -8,7 +8,7 @@ Per dtype (float32, float16), near_sym_a (5 / 7 taps) and near_sym_b (13 / 19), 
 figures) and at a short-row cell, 4096 x 16 x 1024: the forward under torch.no_grad() (inference), the forward of an input that
 asks for a gradient (training: the directions are stored as well) and forward + backward, on both routes.  float32 near_sym_a
 also sweeps the row length from 64 to 4096 samples at 2^26 samples in all: one wave serves one row, so this is where the fused
-route can lose, and where ops.SCAT1D_MIN_LEN is read off.  Times are medians of device-event intervals over `reps` (>= 20)
+route can lose (it does not: ops.scat1d_covered sets no shortest row).  Times are medians of device-event intervals over `reps` (>= 20)
 steps after warm-up, the two routes taking turns inside one timing loop; the spread of a cell is the interquartile range of its
 steps.  A cell is a WIN of the fused route only when its median is below the composition's by more than the two spreads
 together.  Next to each cell: the fused route's algorithmic bytes - 2 signal sizes for the inference forward (x in, Z out), 3 for
@@ -113,7 +113,6 @@ def child(dtype_name, reps):
     import torch
     import pytorch_wavelets_amd as pw
     from pytorch_wavelets_amd import ops
-    ops.SCAT1D_MIN_LEN = 0                                  # (the policy is what this probe is there to set)
     dev = torch.device('cuda:0')
     dtype = getattr(torch, dtype_name)
     res = {}
